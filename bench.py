@@ -2,9 +2,23 @@
 """Headline benchmark: device-resident 4+2 EC encode + reconstruct of batched
 1 MiB objects on MI355X (BASELINE.json metric, configs[1] + configs[2]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does only what the headline needs: set up the batch, warm up,
+time the K steps, check the rebuilt shards, write the outputs if
+--dump-outputs is given, and print the JSON line (metric, value, ms_per_step,
+roofline of the timed launches).  Every other leg named below (cpu_baseline,
+config5, small_objects, config4, odd_objects, random_objects, mid_objects,
+batch_split, host_path) runs only with --full.
+
+--dump-outputs DIR writes what the last timed step left in the arrays a
+caller of the two ops receives, as DIR/parity.npy (Encode's parity shards)
+and DIR/rebuilt.npy (Reconstruct's rebuilt shards), float32, byte values;
+an array of more than DUMP_MAX_ELEMS bytes is sampled at fixed, seeded flat
+indices.  The objects are splitmix64 streams of their global index, so the
+same arguments give the same inputs, and the same outputs, on every run.
 
 One step = one pass of the hot path over one batch held in HBM:
   1. Encoder.Encode   of 4096 objects x 1 MiB  (4 data shards read, 2 parity written)
@@ -17,7 +31,8 @@ ranks (rank r owns global objects [r*4096, (r+1)*4096)): weak scaling, no
 data-path collective; torch.distributed carries only the barrier and the
 max-time reduction.
 
-Extra objects on the JSON line: `roofline` (dominant kernel = the
+Extra objects on the JSON line (all but `roofline` with --full only):
+`roofline` (dominant kernel = the
 gf_apply_vec_pipe2<4,2> kernel that both ops launch, as `dispatches_per_op`
 dispatches of 1024 objects each (tuning.h HBEC_VEC_CHUNK_TILES); achieved =
 algorithmic bytes per op / the op's HIP-event-timed average duration on the
@@ -203,6 +218,32 @@ class Workload:
         torch.cuda.synchronize()
         want = torch.cat([self.objs[:, i * self.s:(i + 1) * self.s] for i in self.erased], dim=1)
         return bool(torch.equal(self.rebuilt, want))
+
+
+# --dump-outputs: elements written per array (float32: 16 MiB each, two arrays)
+DUMP_MAX_ELEMS = 1 << 22
+DUMP_SEED = 0x48424F55
+
+
+def dump_outputs(out_dir, arrays, rank=0):
+    """Write each (name, uint8 device tensor) as out_dir/<name>.npy (rank 0;
+    <name>.rank<r>.npy on the other ranks), float32.  A tensor of more than
+    DUMP_MAX_ELEMS bytes is sampled at DUMP_MAX_ELEMS flat indices drawn once
+    from a fixed seed (sorted, without regard to the contents), so two builds
+    given the same arguments write the same positions."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    for i, (name, t) in enumerate(arrays):
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng(DUMP_SEED + i)
+            idx = np.sort(rng.integers(0, flat.numel(), DUMP_MAX_ELEMS, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        host = flat.cpu().numpy().astype(np.float32)
+        np.save(out_dir / (f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), host)
 
 
 def cpu_baseline(k, m, obj_len, erased, budget_s=12.0, sample_objs=512, gpu=None):
@@ -909,6 +950,13 @@ def parse_args(argv):
                     help="untimed steps before the W warm-up steps until this much GPU time has passed, "
                          "so the clocks have left their start-up ramp (0 = none)")
     ap.add_argument("--objects", type=int, default=4096, help="objects per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the parity and rebuilt shards of the last step as "
+                         "DIR/<name>.npy (float32; a fixed, seeded sample of a large array)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg (CPU baseline and oracle comparison, "
+                         "config 5, small / config 4 / odd / random / mid-size objects, batch split, host path); "
+                         "the --no-* and --*-objects options below choose among them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-small", action="store_true",
@@ -949,6 +997,9 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus, argv)
@@ -1020,6 +1071,8 @@ def main(argv=None):
         pg.barrier()
     elapsed = time.perf_counter() - t0
     ok = w.verify()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, (("parity", w.parity), ("rebuilt", w.rebuilt)), rank)
 
     enc_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in ev) / args.steps
     rec_ms = sum(e1.elapsed_time(e2) for _, e1, e2 in ev) / args.steps
@@ -1100,7 +1153,7 @@ def main(argv=None):
             "parity_ok": ok,
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ns = min(512, n)
             gpu = (w.objs[:ns].cpu().numpy(), w.parity[:ns].cpu().numpy(), w.rebuilt[:ns].cpu().numpy())
             line["cpu_baseline"] = cpu_baseline(k, m, obj_len, erased, budget_s=args.cpu_budget, sample_objs=ns,
@@ -1108,6 +1161,12 @@ def main(argv=None):
             del gpu
     del w  # free this rank's headline batch before the partition / split buffers
     torch.cuda.empty_cache()
+    if not args.full:  # a plain run ends with the headline
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if pg:
+            pg.destroy_process_group()
+        return 0 if ok else 3
     if args.config5_objects > 0:
         c5 = config5(pg, k, m, obj_len, args.config5_objects, world, rank, ctl_device)
         if rank == 0:

@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 T=${TAG:-r06}
 if [ "${1:-all}" = "second" ]; then
-  timeout -k 10 500 python bench.py > $OUT/${T}_bench2.json 2> $OUT/${T}_bench2.err || exit 1
+  timeout -k 10 500 python bench.py --full > $OUT/${T}_bench2.json 2> $OUT/${T}_bench2.err || exit 1
   tail -c 200 $OUT/${T}_bench2.json
   bash scripts/gpu_run.sh prof || exit 1
   bash scripts/sq_odd.sh ${T}final o42,o63,o83,o104,o124,v83,v104,v124,r83,r104,x83 > $OUT/${T}final_sq.log 2>&1 || exit 1
@@ -21,7 +21,7 @@ tail -2 $OUT/${T}_smoke.log
 bash scripts/gpu_run.sh pmcfetch pmcwrite || exit 1
 python scripts/pmc_summary.py $OUT/pmc_fetch $OUT/pmc_write $OUT/${T}_pmc.json > /dev/null || exit 1
 cp $OUT/${T}_pmc.json profiles/${T}_pmc.json
-timeout -k 10 500 python bench.py > $OUT/${T}_bench.json 2> $OUT/${T}_bench.err || exit 1
+timeout -k 10 500 python bench.py --full > $OUT/${T}_bench.json 2> $OUT/${T}_bench.err || exit 1
 tail -c 300 $OUT/${T}_bench.json
 [ "${1:-all}" = "first" ] && { echo first-done; exit 0; }
 bash scripts/gpu_run.sh prof || exit 1

@@ -26,18 +26,18 @@ for s in "$@"; do
     tests) step tests 900 python -u -m pytest tests -m gpu -x -v --tb=short --timeout 120 --timeout-method thread -p no:cacheprovider ;;
     testsall) step testsall 900 python -m pytest tests -m gpu -q -p no:cacheprovider ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py --steps 50 --warmup 10 ;;
+    bench) step bench 600 python bench.py --full --steps 50 --warmup 10 ;;
     prof)
       mkdir -p "$OUT/prof"
-      (cd /tmp && step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 "$ROOT/bench.py" --steps 50 --warmup 10 --no-cpu-baseline --no-host-path --config5-objects 0) || exit $?
+      (cd "$TMPDIR" && step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 "$ROOT/bench.py" --full --steps 50 --warmup 10 --no-cpu-baseline --no-host-path --config5-objects 0) || exit $?
       ;;
     pmcfetch)
       mkdir -p "$OUT/pmc_fetch"
-      (cd /tmp && step pmcfetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 "$ROOT/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-host-path --config5-objects 0) || exit $?
+      (cd "$TMPDIR" && step pmcfetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 "$ROOT/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-host-path --config5-objects 0) || exit $?
       ;;
     pmcwrite)
       mkdir -p "$OUT/pmc_write"
-      (cd /tmp && step pmcwrite 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_write" -o run -- python3 "$ROOT/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-host-path --config5-objects 0) || exit $?
+      (cd "$TMPDIR" && step pmcwrite 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_write" -o run -- python3 "$ROOT/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-host-path --config5-objects 0) || exit $?
       ;;
     cfgprof)
       mkdir -p "$OUT/cfgprof"
@@ -64,7 +64,7 @@ for s in "$@"; do
       (cd /tmp && step smallpmcwrite 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/small_pmc_write" -o run -- python3 "$ROOT/scripts/bench_small.py") || exit $?
       ;;
     small) step small 300 python scripts/bench_small.py ;;
-    dist2) step dist2 600 env HBEC_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 10 --warmup 2 --objects 2048 ;;
+    dist2) step dist2 600 env HBEC_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --steps 10 --warmup 2 --objects 2048 ;;
     configs) step configs 600 python scripts/bench_configs.py ;;
     host) step host 600 python scripts/bench_host.py ;;
     ecloops)
