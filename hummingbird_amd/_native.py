@@ -67,6 +67,10 @@ _SIG = [
     ("hbec_encode_batch", C.c_int, [_P, C.POINTER(View), C.c_uint64, C.c_uint64, _P]),
     ("hbec_reconstruct_batch", C.c_int,
      [_P, C.POINTER(View), _U8P, C.c_uint64, C.c_uint64, C.c_int, _P]),
+    ("hbec_reconstruct_batch_mixed", C.c_int,
+     [_P, C.POINTER(View), _U8P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64, C.c_int, _P]),
+    ("hbec_mixed_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_set_mixed_chunk_tiles", C.c_int, [C.c_uint64]),
     ("hbec_md5_batch", C.c_int, [C.POINTER(View), C.c_int, C.c_uint64, C.c_uint64, _P, _P]),
     ("hbec_md5_list", C.c_int, [C.POINTER(_P), C.POINTER(C.c_uint64), C.c_uint64, _P, _P]),
     ("hbec_md5_host", C.c_int, [C.POINTER(_P), C.POINTER(C.c_uint64), C.c_uint64, _U8P]),

@@ -60,6 +60,46 @@ def reconstruct_views(enc: Encoder, views, present, n_objects: int, shard_len: i
                                          _stream_ptr(stream)))
 
 
+def reconstruct_views_mixed(enc: Encoder, views, present, n_objects: int, shard_len: int, data_only: bool = False,
+                            stream=None) -> None:
+    """reconstruct_views with an erasure pattern per object: ``present`` is an
+    [n_objects, k+m] array, row o the mask of object o (non-zero = shard read).
+    Equal rows share one pattern (hbec_reconstruct_batch_mixed)."""
+    import numpy as np
+
+    v = _views(views)
+    p = np.asarray(present) != 0
+    if p.ndim != 2 or p.shape[0] != int(n_objects) or p.shape[1] != len(views):
+        raise ValueError("present must be [n_objects, k+m]")
+    patterns, pattern_of = np.unique(p.astype(np.uint8), axis=0, return_inverse=True)
+    patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+    pattern_of = np.ascontiguousarray(pattern_of.reshape(-1), dtype=np.uint32)
+    check(N.lib().hbec_reconstruct_batch_mixed(
+        enc.handle, v, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+        pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), int(n_objects), int(shard_len), int(data_only),
+        _stream_ptr(stream)))
+
+
+def mixed_tile_bytes(k: int) -> int:
+    """Shard bytes per wave tile of the mixed kernel for k data shards
+    (kernels.h stripes_u: 4 / k KiB up to k = 4, 1 KiB above)."""
+    return 1024 * (4 // k if k <= 4 else 1)
+
+
+def mixed_stats():
+    """Launches since load of hbec_reconstruct_batch_mixed: of the mixed kernel
+    (`mixed`), and of the single-pattern path, one per run of equal-pattern
+    objects (`runs`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_mixed_stats(C.byref(a), C.byref(b)))
+    return {"mixed": a.value, "runs": b.value}
+
+
+def set_mixed_chunk_tiles(tiles: int) -> None:
+    """Test hook: mixed-kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_mixed_chunk_tiles(int(tiles)))
+
+
 def verify_views(enc: Encoder, views, n_objects: int, shard_len: int, flags, stream=None) -> None:
     """Set flags[o] = 1 (uint32 CUDA tensor, caller-zeroed) for objects whose parity is wrong."""
     v = _views(views)

@@ -30,6 +30,7 @@
 #include "gf256.h"
 #include "internal.h"
 #include "kernels.h"
+#include "mixed.h"
 
 namespace hbec {
 
@@ -910,6 +911,194 @@ static int direct_reconstruct(hbec_codec* c, uint8_t* base, uint64_t s, const ui
 
 static const DirectFns kDirect = {direct_encode, direct_reconstruct};
 
+// ---------------------------------------------------------------------------
+// Reconstruct with an erasure pattern per object (gf_apply_mixed, mixed.hip)
+// ---------------------------------------------------------------------------
+static std::atomic<uint64_t> g_mixed_launches{0}, g_run_launches{0};
+// test hook (hbec_set_mixed_chunk_tiles): tiles per launch of the mixed kernel
+static std::atomic<uint64_t> g_mixed_chunk_override{0};
+// How a launch's waves walk its tiles.  Grid-stride (gf_apply_stripes' walk)
+// streams long shards best, but a wave then advances waves / tiles_per_obj
+// entries per tile and reloads its tables whenever that crosses into another
+// record; a contiguous run of the sorted list per wave meets few records.
+// 4096 x 1 MiB 4+2 (a step crosses a record every 17th tile): grid-stride
+// 1.10 ms, contiguous 1.27 ms; 65 536 x 4 KiB 8+3 (every tile): 0.214 vs
+// 0.151 ms (profiles/mixed_walk_ab.jsonl).  So: contiguous when a grid-stride
+// step would cross a record more often than every 4th tile.  Tuning knob:
+// 0 / 1 force grid-stride / contiguous.
+static const int g_mixed_contig = (int)tune_knob("HBEC_MIXED_CONTIG", -1);
+static bool mixed_contiguous(uint64_t waves, uint64_t tiles_per_obj, uint64_t entries, uint64_t records) {
+    if (g_mixed_contig >= 0) return g_mixed_contig != 0;
+    return waves * records * 4 > tiles_per_obj * entries;
+}
+
+// One distinct pattern of a mixed call, resolved.
+struct MixedPattern {
+    std::vector<int> surv, outs;
+    std::vector<uint8_t> rows;  // outs.size() x k
+    uint64_t uses = 0;          // objects of the batch with this pattern
+    uint32_t rec = 0;           // its record (fast route)
+};
+
+// The run route: one apply_views call per run of consecutive objects with the
+// same pattern, the views advanced to the run's first object.  Correct for
+// every shape the library supports.
+static int mixed_runs(const hbec_codec* c, const hbec_view* views, const std::vector<MixedPattern>& pats,
+                      const uint32_t* pattern_of, uint64_t n_objects, uint64_t shard_len, hipStream_t stream) {
+    std::vector<hbec_view> vin((size_t)c->k), vout;
+    for (uint64_t o0 = 0; o0 < n_objects;) {
+        uint64_t o1 = o0 + 1;
+        while (o1 < n_objects && pattern_of[o1] == pattern_of[o0]) ++o1;
+        const MixedPattern& p = pats[pattern_of[o0]];
+        if (!p.outs.empty()) {
+            auto at = [&](int i) {
+                return hbec_view{static_cast<uint8_t*>(views[i].base) + o0 * views[i].obj_stride, views[i].obj_stride};
+            };
+            vout.resize(p.outs.size());
+            for (size_t j = 0; j < p.surv.size(); ++j) vin[j] = at(p.surv[j]);
+            for (size_t r = 0; r < p.outs.size(); ++r) vout[r] = at(p.outs[r]);
+            g_run_launches.fetch_add(1, std::memory_order_relaxed);
+            const int rc = apply_views((int)p.outs.size(), c->k, p.rows.data(), vin.data(), vout.data(), o1 - o0,
+                                       shard_len, stream);
+            if (rc) return rc;
+        }
+        o0 = o1;
+    }
+    return HBEC_OK;
+}
+
+// The fast route: records of the patterns with outputs (ordered by output
+// count) and the {object, record} entries sorted by record, uploaded to
+// stream-ordered scratch; per output count r the entries are one contiguous
+// slice, coded by launches of gf_apply_mixed<k, r> over at most the chunk
+// limit's tiles of whole objects.
+static int mixed_fast(const hbec_codec* c, const hbec_view* views, std::vector<MixedPattern>& pats,
+                      const uint32_t* pattern_of, uint64_t n_objects, uint64_t shard_len, hipStream_t stream) {
+    const int k = c->k;
+    std::vector<MixedRec> recs;
+    uint64_t slice[kMaxR + 2] = {};  // entries of output count r: [slice[r], slice[r + 1])
+    std::vector<uint64_t> first;     // first entry of each record
+    uint64_t n_ent = 0;
+    for (int r = 1; r <= kMaxR; ++r) {
+        slice[r] = n_ent;
+        for (MixedPattern& p : pats) {
+            if (!p.uses || (int)p.outs.size() != r) continue;
+            MixedRec m;
+            std::memset(&m, 0, sizeof(m));
+            for (int j = 0; j < k; ++j) {
+                m.in_base[j] = reinterpret_cast<uint64_t>(views[p.surv[j]].base);
+                m.in_stride[j] = views[p.surv[j]].obj_stride;
+            }
+            for (int q = 0; q < r; ++q) {
+                m.out_base[q] = reinterpret_cast<uint64_t>(views[p.outs[q]].base);
+                m.out_stride[q] = views[p.outs[q]].obj_stride;
+                for (int j = 0; j < k; ++j) perm_table(p.rows[(size_t)q * k + j], m.tab[q][j]);
+            }
+            p.rec = (uint32_t)recs.size();
+            recs.push_back(m);
+            first.push_back(n_ent);
+            n_ent += p.uses;
+        }
+    }
+    slice[kMaxR + 1] = n_ent;
+    if (n_ent == 0) return HBEC_OK;
+    std::vector<MixedEnt> ents((size_t)n_ent);
+    for (uint64_t o = 0; o < n_objects; ++o) {
+        const MixedPattern& p = pats[pattern_of[o]];
+        if (p.outs.empty()) continue;
+        ents[(size_t)first[p.rec]++] = MixedEnt{(uint32_t)o, p.rec};
+    }
+
+    int dev = 0, cus = 0;
+    int rc = current_device(&dev);
+    if (rc) return rc;
+    rc = cu_count(dev, &cus);
+    if (rc) return rc;
+    const size_t rec_bytes = recs.size() * sizeof(MixedRec), ent_bytes = ents.size() * sizeof(MixedEnt);
+    void* d = nullptr;
+    rc = scratch_alloc(rec_bytes + ent_bytes, stream, &d);
+    if (rc) return rc;
+    const MixedRec* d_recs = static_cast<const MixedRec*>(d);
+    const MixedEnt* d_ents = reinterpret_cast<const MixedEnt*>(static_cast<const uint8_t*>(d) + rec_bytes);
+    // pageable sources: staged by the runtime before the calls return
+    hipError_t e = hipMemcpyAsync(d, recs.data(), rec_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(const_cast<MixedEnt*>(d_ents), ents.data(), ent_bytes, hipMemcpyHostToDevice, stream);
+
+    const uint64_t tile = (uint64_t)mixed_tile_bytes(k);
+    const uint64_t tpo = (shard_len + tile - 1) / tile;
+    const uint64_t hook = g_mixed_chunk_override.load(std::memory_order_relaxed);
+    // keep n_tiles < 2^31 per launch: split the entries (whole objects)
+    const uint64_t max_ent = std::max<uint64_t>(1, std::min<uint64_t>((1ull << 31) - 1, hook ? hook : g_vec_chunk_tiles) / tpo);
+    constexpr uint64_t wpb = kBlockThreads / 64;
+    for (int r = 1; r <= kMaxR && e == hipSuccess; ++r) {
+        for (uint64_t e0 = slice[r]; e0 < slice[r + 1] && e == hipSuccess; e0 += max_ent) {
+            const uint64_t ne = std::min(max_ent, slice[r + 1] - e0);
+            MixedArgs a;
+            a.n_tiles = (uint32_t)(ne * tpo);
+            a.tiles_per_obj = (uint32_t)tpo;
+            a.shard_len = (uint32_t)shard_len;
+            int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((a.n_tiles + wpb - 1) / wpb, (uint64_t)cus));
+            if (g_grid_cap > 0) grid = std::min(grid, g_grid_cap);
+            const uint64_t waves = (uint64_t)grid * wpb;
+            a.iters = (uint32_t)((a.n_tiles + waves - 1) / waves);
+            // the entries are sorted by record and every record is used
+            const uint64_t n_recs = ents[(size_t)(e0 + ne - 1)].rec - ents[(size_t)e0].rec + 1;
+            const bool contig = mixed_contiguous(waves, tpo, ne, n_recs);
+            a.wave_step = contig ? a.iters : 1u;
+            a.iter_step = contig ? 1u : (uint32_t)waves;
+            g_mixed_launches.fetch_add(1, std::memory_order_relaxed);
+            e = launch_mixed(k, r, a, d_recs, d_ents + e0, grid, stream);
+        }
+    }
+    scratch_free(d, stream);
+    if (e != hipSuccess) return hip_fail(e, "launch gf_apply_mixed");
+    return HBEC_OK;
+}
+
+static int reconstruct_mixed(hbec_codec* c, const hbec_view* views, const uint8_t* patterns, uint32_t n_patterns,
+                             const uint32_t* pattern_of, uint64_t n_objects, uint64_t shard_len, bool data_only,
+                             hipStream_t stream) {
+    if (!c || !views || !patterns || !pattern_of) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    if (n_patterns > 65536) return fail(HBEC_ERR_INVALID_ARG, "more than 65536 patterns");
+    if (n_objects && !n_patterns) return fail(HBEC_ERR_INVALID_ARG, "objects but no patterns");
+    const int k = c->k, n = c->k + c->m;
+    std::vector<MixedPattern> pats(n_patterns);
+    std::vector<std::vector<uint8_t>> masks(n_patterns);
+    for (uint32_t p = 0; p < n_patterns; ++p) {
+        masks[p].assign(patterns + (size_t)p * n, patterns + (size_t)(p + 1) * n);
+        int n_present = 0;
+        for (auto& v : masks[p]) n_present += (v = v ? 1 : 0);
+        if (n_present < k) return fail(HBEC_ERR_TOO_FEW_SHARDS, "too few shards given (pattern " + std::to_string(p) + ")");
+    }
+    for (uint64_t o = 0; o < n_objects; ++o) {
+        if (pattern_of[o] >= n_patterns)
+            return fail(HBEC_ERR_INVALID_ARG, "pattern index out of range (object " + std::to_string(o) + ")");
+        ++pats[pattern_of[o]].uses;
+    }
+    // every view some object reads or writes; the route of the whole call
+    bool fast = k <= kMixedMaxK && shard_len % 16 == 0 && pos32_shard(shard_len) && n_objects < (1ull << 32);
+    for (uint32_t p = 0; p < n_patterns; ++p) {
+        MixedPattern& mp = pats[p];
+        if (!mp.uses) continue;
+        int rc = decode_rows(c, masks[p], data_only, mp.surv, mp.outs, mp.rows);
+        if (rc) return rc;
+        if (mp.outs.empty()) continue;  // nothing to rebuild: its objects are left untouched
+        fast = fast && (int)mp.outs.size() <= kMaxR;
+        auto use = [&](int i) {
+            fast = fast && aligned16(views[i].base) && views[i].obj_stride % 16 == 0;
+            return views[i].base != nullptr;
+        };
+        for (int i : mp.surv)
+            if (!use(i)) return fail(HBEC_ERR_INVALID_ARG, "null view base (shard " + std::to_string(i) + ")");
+        for (int i : mp.outs)
+            if (!use(i)) return fail(HBEC_ERR_INVALID_ARG, "null view base (shard " + std::to_string(i) + ")");
+    }
+    if (n_objects == 0 || shard_len == 0) return HBEC_OK;
+    return fast ? mixed_fast(c, views, pats, pattern_of, n_objects, shard_len, stream)
+                : mixed_runs(c, views, pats, pattern_of, n_objects, shard_len, stream);
+}
+
 }  // namespace hbec
 
 using namespace hbec;
@@ -1076,6 +1265,31 @@ int hbec_reconstruct_batch(hbec_codec* c, const hbec_view* views, const uint8_t*
         for (size_t o = 0; o < outs.size(); ++o) vout[o] = views[outs[o]];
         return apply_views((int)outs.size(), c->k, rows.data(), vin.data(), vout.data(), n_objects, shard_len,
                            static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_reconstruct_batch_mixed(hbec_codec* c, const hbec_view* views, const uint8_t* patterns, uint32_t n_patterns,
+                                 const uint32_t* pattern_of, uint64_t n_objects, uint64_t shard_len, int data_only,
+                                 void* hip_stream) {
+    return hbec::guarded("hbec_reconstruct_batch_mixed", [&]() -> int {
+        return reconstruct_mixed(c, views, patterns, n_patterns, pattern_of, n_objects, shard_len, data_only != 0,
+                                 static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_mixed_stats(uint64_t* mixed_launches, uint64_t* run_launches) {
+    return hbec::guarded("hbec_mixed_stats", [&]() -> int {
+        if (!mixed_launches || !run_launches) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *mixed_launches = g_mixed_launches.load(std::memory_order_relaxed);
+        *run_launches = g_run_launches.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_set_mixed_chunk_tiles(uint64_t tiles) {
+    return hbec::guarded("hbec_set_mixed_chunk_tiles", [&]() -> int {
+        g_mixed_chunk_override.store(tiles, std::memory_order_relaxed);
+        return HBEC_OK;
     });
 }
 

@@ -163,6 +163,30 @@ int hbec_encode_batch(hbec_codec* codec, const hbec_view* views, uint64_t n_obje
 int hbec_reconstruct_batch(hbec_codec* codec, const hbec_view* views, const uint8_t* present, uint64_t n_objects,
                            uint64_t shard_len, int data_only, void* hip_stream);
 
+/* hbec_reconstruct_batch with a pattern per object.  patterns: n_patterns rows
+ * of k+m bytes (host), row p a `present` mask as in hbec_reconstruct_batch.
+ * pattern_of: n_objects indices into patterns (host).  Object o is rebuilt
+ * exactly as hbec_reconstruct_batch would rebuild it with patterns[pattern_of[o]]:
+ * survivors = its first k present shards, every missing shard written (data
+ * shards only when data_only), nothing else of the object read or written.
+ * The (object, shard) regions of the batch must be pairwise disjoint.  Both
+ * arrays are copied before the call returns.  Queued on hip_stream.
+ * 16-B-aligned views and shard lengths with k <= 8 and at most 4 shards to
+ * rebuild per object are coded by one kernel launch per distinct number of
+ * rebuilt shards (and per 256 Ki tiles); every other shape by one
+ * hbec_reconstruct_batch-style launch per run of consecutive objects with
+ * the same pattern.  Errors (a null argument, n_patterns == 0 with objects or
+ * > 65536, an index >= n_patterns, a null base of a view some object uses:
+ * HBEC_ERR_INVALID_ARG; a listed pattern with fewer than k present:
+ * HBEC_ERR_TOO_FEW_SHARDS) are found before anything is queued. */
+int hbec_reconstruct_batch_mixed(hbec_codec* codec, const hbec_view* views, const uint8_t* patterns,
+                                 uint32_t n_patterns, const uint32_t* pattern_of, uint64_t n_objects,
+                                 uint64_t shard_len, int data_only, void* hip_stream);
+/* launches since load: of the mixed kernel, and of per-run launches of the single-pattern path */
+int hbec_mixed_stats(uint64_t* mixed_launches, uint64_t* run_launches);
+/* test hook, as hbec_set_odd_chunk_tiles: tiles per launch of the mixed kernel (0 = default) */
+int hbec_set_mixed_chunk_tiles(uint64_t tiles);
+
 /* Verify a batch (read-only stream over k+m shards per object): sets
  * d_flags[o] (device memory, n_objects uint32, caller-zeroed) to 1 for every
  * object whose stored parity differs from the recomputed parity. */
