@@ -91,6 +91,10 @@ _SIG = [
      [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_encode_plan", C.c_int, [_P, _P, _P]),
     ("hbec_reconstruct_plan", C.c_int, [_P, _P, _U8P, C.c_int, _P]),
+    ("hbec_verify_plan", C.c_int, [_P, _P, _P, _P]),
+    ("hbec_verify_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_verify_plan_tile_bytes", C.c_int, [C.c_int]),
+    ("hbec_verify_host", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64, _U8P]),
     ("hbec_encode_host", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64]),
     ("hbec_host_alloc", C.c_int, [C.c_size_t, C.POINTER(_P)]),
     ("hbec_host_free", None, [_P]),

@@ -146,6 +146,7 @@ class StripePlan:
         regions, hbec_plan_objects)."""
         self.enc = enc
         self._h = C.c_void_p()
+        self._n = len(objects) if objects is not None else len(stripes)
         if objects is not None:
             arr = (N.Object * max(1, len(objects)))()
             for i, (d, p, s) in enumerate(objects):
@@ -176,6 +177,32 @@ class StripePlan:
     def reconstruct(self, present, data_only=False, stream=None):
         p = (C.c_uint8 * len(present))(*[1 if x else 0 for x in present])
         check(N.lib().hbec_reconstruct_plan(self.enc.handle, self._h, p, int(data_only), _stream_ptr(stream)))
+
+    def verify(self, flags, stream=None):
+        """flags[i] |= 1 (uint32 CUDA tensor of len(stripes), caller-zeroed) for
+        every stripe / object i whose stored parity differs from the recomputed
+        one (hbec_verify_plan).  Read-only; queued on the stream."""
+        import torch
+
+        if flags.dtype != torch.uint32 and flags.dtype != torch.int32:
+            raise ValueError("flags must be a 32-bit integer tensor")
+        if not flags.is_cuda or not flags.is_contiguous() or flags.numel() < self._n:
+            raise ValueError("flags must be a contiguous CUDA tensor with one entry per stripe")
+        check(N.lib().hbec_verify_plan(self.enc.handle, self._h, C.c_void_p(flags.data_ptr()), _stream_ptr(stream)))
+
+
+def verify_plan_stats():
+    """Since load: launches of the plan Verify kernels (`plan_launches`) and
+    verify calls made one stripe at a time for the shapes those kernels do not
+    take (`per_stripe_calls`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_verify_plan_stats(C.byref(a), C.byref(b)))
+    return {"plan_launches": a.value, "per_stripe_calls": b.value}
+
+
+def verify_plan_tile_bytes(k: int) -> int:
+    """Shard bytes per wave tile of the any-alignment plan Verify kernel."""
+    return int(N.lib().hbec_verify_plan_tile_bytes(int(k)))
 
 
 KERNEL_KINDS = {0: "unrolled", 1: "pipelined", 2: "streaming", 3: "packed", 4: "records"}

@@ -39,6 +39,7 @@
 #include "internal.h"
 #include "kernels.h"
 #include "pool.h"
+#include "vplan.h"
 
 using hbec::fail;
 using hbec::hip_fail;
@@ -931,6 +932,153 @@ int host_run_on(Ring* ring, const hbec_stripe* stripes, uint64_t n, const std::v
     return HBEC_OK;
 }
 
+// ---- Verify of host stripes (hbec_verify_host) ----
+// Read-only, so nothing but the flags comes back.  Pinned stripes are read in
+// place over PCIe by the plan Verify kernels on records over their device
+// addresses.  Every other stripe is one contiguous block of (k+m) S bytes:
+// one copy into the pinned IN slot at a 16-B-aligned offset, H2D, and the
+// same kernels over records of the device slot; a stripe larger than a slot
+// is cut into column pieces ((k+m) copies each) that OR into its flag.  A slot
+// is reused once the kernel that read it is done (ev_cmp).
+struct VPiece {
+    uint64_t stripe, col, len, off;  // off: the piece's (k+m) x len block in the slot
+    bool whole;                      // col == 0 and len == S: one copy
+};
+
+int verify_host_run_on(Ring* ring, hbec_codec* codec, const hbec_stripe* stripes, uint64_t n, uint8_t* flags) {
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+    const uint64_t L = (uint64_t)(k + m);
+    const bool fast = hbec::vp_fast_shape(k, m);
+    hipStream_t st = ring->s_cmp;
+    hbec::VerifyRecs zc;  // pinned stripes
+    std::vector<uint64_t> staged;
+    for (uint64_t s = 0; s < n; ++s) {
+        const uint64_t S = stripes[s].shard_len;
+        if (S == 0) continue;
+        const uint64_t d = pinned_device_addr(stripes[s].base, L * S);
+        if (!d) staged.push_back(s);
+        else if (!hbec::vp_add(zc, k, m, d, d + (uint64_t)k * S, S, s))
+            return fail(HBEC_ERR_INVALID_ARG, "too many tiles in one call");
+    }
+    // device flags, then the coefficient tables (stream-ordered scratch)
+    std::vector<uint32_t> tab;
+    if (fast) hbec::verify_tab(codec, tab);
+    const size_t flag_bytes = ((size_t)n * 4 + 15) & ~(size_t)15;
+    void* d_mem = nullptr;
+    int rc = hbec::scratch_alloc(flag_bytes + tab.size() * 4, st, &d_mem);
+    if (rc) return rc;
+    struct Scratch {
+        std::vector<void*> p;
+        hipStream_t s;
+        ~Scratch() {
+            for (void* q : p) hbec::scratch_free(q, s);
+        }
+    } scratch{{d_mem}, st};
+    uint32_t* d_flags = static_cast<uint32_t*>(d_mem);
+    const uint32_t* d_tab = reinterpret_cast<const uint32_t*>(static_cast<uint8_t*>(d_mem) + flag_bytes);
+    hipError_t e = hipMemsetAsync(d_flags, 0, (size_t)n * 4, st);
+    if (e == hipSuccess && !tab.empty()) e = hbec::launch_put_words(const_cast<uint32_t*>(d_tab), tab.data(), tab.size() * 4, st);
+    if (e != hipSuccess) return hip_fail(e, "verify host flags");
+
+    if (!zc.recs.empty()) {
+        void* d_rec = nullptr;
+        const size_t rb = zc.recs.size() * sizeof(hbec::VRec), tb = zc.tiles.size() * sizeof(hbec::VTile);
+        rc = hbec::scratch_alloc(rb + tb, st, &d_rec);
+        if (rc) return rc;
+        scratch.p.push_back(d_rec);
+        e = hipMemcpyAsync(d_rec, zc.recs.data(), rb, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && tb)
+            e = hipMemcpyAsync(static_cast<uint8_t*>(d_rec) + rb, zc.tiles.data(), tb, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return hip_fail(e, "verify host records H2D");
+        rc = hbec::verify_recs_run(codec, static_cast<const hbec::VRec*>(d_rec), zc.recs.size(),
+                                   reinterpret_cast<const hbec::VTile*>(static_cast<uint8_t*>(d_rec) + rb),
+                                   zc.tiles.size(), d_tab, d_flags, st, zero_copy_max_blocks());
+        if (rc) return rc;
+    }
+    for (const hbec::VOther& o : zc.other) {
+        rc = hbec::verify_other_run(codec, o, d_flags, st);
+        if (rc) return rc;
+    }
+
+    if (!staged.empty()) {
+        rc = ring_staging_init(*ring);
+        if (rc) return rc;
+        const uint64_t max_cols = (ring->in_cap / L / 16) * 16;
+        if (max_cols < 16) return fail(HBEC_ERR_INVALID_ARG, "staging slot too small");
+        const uint64_t rec_cap = (uint64_t)ring->tile_cap * sizeof(hbec::TileRec);
+        auto rec_bytes = [](uint64_t len) {
+            return sizeof(hbec::VRec) + (uint64_t)((hbec::vp_main_bytes((uint32_t)len) + hbec::kVpTile - 1) / hbec::kVpTile) *
+                                            sizeof(hbec::VTile);
+        };
+        std::vector<std::vector<VPiece>> chunks(1);
+        uint64_t used = 0, rused = 0;
+        for (uint64_t s : staged) {
+            const uint64_t S = stripes[s].shard_len;
+            const bool whole = L * S <= ring->in_cap;
+            for (uint64_t col = 0; col < S; col += whole ? S : max_cols) {
+                const uint64_t len = whole ? S : std::min(max_cols, S - col);
+                const uint64_t bytes = (L * len + 15) & ~(uint64_t)15, rb = rec_bytes(len);
+                if (used + bytes > ring->in_cap || rused + rb > rec_cap) {
+                    chunks.emplace_back();
+                    used = rused = 0;
+                }
+                chunks.back().push_back({s, col, len, used, whole});
+                used += bytes;
+                rused += rb;
+            }
+        }
+        for (size_t c = 0; c < chunks.size(); ++c) {
+            const int slot = (int)(c % kSlots);
+            e = hipEventSynchronize(ring->ev_cmp[slot]);  // the kernel that read this slot is done
+            if (e != hipSuccess) return hip_fail(e, "verify host slot wait");
+            const auto& pieces = chunks[c];
+            ring->pool->parallel_for(pieces.size(), [&](size_t i) {
+                const VPiece& p = pieces[i];
+                const uint8_t* src = static_cast<const uint8_t*>(stripes[p.stripe].base);
+                uint8_t* dst = ring->pin_in[slot] + p.off;
+                if (p.whole) {
+                    std::memcpy(dst, src, L * p.len);
+                    return;
+                }
+                const uint64_t S = stripes[p.stripe].shard_len;
+                for (uint64_t j = 0; j < L; ++j) std::memcpy(dst + j * p.len, src + j * S + p.col, p.len);
+            });
+            const uint64_t din = reinterpret_cast<uint64_t>(ring->dev_in[slot]);
+            hbec::VerifyRecs vr;
+            uint64_t in_bytes = 0;
+            for (const VPiece& p : pieces) {
+                (void)hbec::vp_add(vr, k, m, din + p.off, din + p.off + (uint64_t)k * p.len, p.len, p.stripe);
+                in_bytes = std::max(in_bytes, p.off + L * p.len);
+            }
+            const size_t rb = vr.recs.size() * sizeof(hbec::VRec), tb = vr.tiles.size() * sizeof(hbec::VTile);
+            uint8_t* prec = reinterpret_cast<uint8_t*>(ring->pin_tiles[slot]);
+            if (rb) std::memcpy(prec, vr.recs.data(), rb);
+            if (tb) std::memcpy(prec + rb, vr.tiles.data(), tb);
+            e = hipSuccess;
+            if (rb + tb) e = hipMemcpyAsync(ring->dev_tiles[slot], prec, rb + tb, hipMemcpyHostToDevice, ring->s_h2d);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(ring->dev_in[slot], ring->pin_in[slot], in_bytes, hipMemcpyHostToDevice, ring->s_h2d);
+            if (e == hipSuccess) e = hipEventRecord(ring->ev_h2d[slot], ring->s_h2d);
+            if (e == hipSuccess) e = hipStreamWaitEvent(st, ring->ev_h2d[slot], 0);
+            if (e != hipSuccess) return hip_fail(e, "verify host H2D");
+            const uint8_t* drec = reinterpret_cast<const uint8_t*>(ring->dev_tiles[slot]);
+            rc = hbec::verify_recs_run(codec, reinterpret_cast<const hbec::VRec*>(drec), vr.recs.size(),
+                                       reinterpret_cast<const hbec::VTile*>(drec + rb), vr.tiles.size(), d_tab, d_flags,
+                                       st);
+            for (size_t i = 0; i < vr.other.size() && !rc; ++i) rc = hbec::verify_other_run(codec, vr.other[i], d_flags, st);
+            if (rc) return rc;
+            e = hipEventRecord(ring->ev_cmp[slot], st);
+            if (e != hipSuccess) return hip_fail(e, "verify host event");
+        }
+    }
+    std::vector<uint32_t> h(n);
+    e = hipMemcpyAsync(h.data(), d_flags, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e, "verify host flags D2H");
+    for (uint64_t s = 0; s < n; ++s) flags[s] = h[s] ? 1 : 0;
+    return HBEC_OK;
+}
+
 // One process, several GPUs (how a single object server would use a node):
 // stripes are cut into contiguous runs of about equal bytes, one per device,
 // and each run is coded by its own host thread on its device's ring (rings
@@ -1164,6 +1312,34 @@ int hbec_reconstruct_host(hbec_codec* codec, const hbec_stripe* stripes, uint64_
         outs.resize(n_out);
         rows.resize((size_t)n_out * k);
         return host_run(stripes, n_stripes, surv, outs, rows);
+    });
+}
+
+int hbec_verify_host(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n_stripes, uint8_t* flags) {
+    return hbec::guarded("hbec_verify_host", [&]() -> int {
+        if (!codec || (n_stripes && (!stripes || !flags))) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        if (n_stripes >= (1ull << 32)) return fail(HBEC_ERR_INVALID_ARG, "too many stripes in one call");
+        bool any = false;
+        for (uint64_t s = 0; s < n_stripes; ++s) {
+            if (stripes[s].shard_len && !stripes[s].base) return fail(HBEC_ERR_INVALID_ARG, "stripe with null base");
+            any = any || stripes[s].shard_len != 0;
+        }
+        if (n_stripes) std::memset(flags, 0, n_stripes);
+        if (hbec_parity_shards(codec) == 0 || !any) return HBEC_OK;
+        Ring* ring = nullptr;
+        int rc = ring_acquire(&ring);
+        if (rc) return rc;
+        struct Releaser {
+            Ring* r;
+            bool ok = false;
+            ~Releaser() {
+                if (!ok) ring_drain(r);
+                ring_release(r);
+            }
+        } rel{ring};
+        rc = verify_host_run_on(ring, codec, stripes, n_stripes, flags);
+        rel.ok = rc == HBEC_OK;
+        return rc;
     });
 }
 

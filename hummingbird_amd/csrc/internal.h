@@ -94,6 +94,18 @@ int launch_stripe_passes(const TileRec* tiles, uint64_t n_tiles, const std::vect
                          const std::vector<int>& out_idx, const std::vector<uint8_t>& rows, int sel_k,
                          hipStream_t stream, int blocks_per_cu = 0, bool mirror = false, int max_blocks = 0);
 
+// Verify over records (vplan.h; plan.cpp): the codec's parity coefficient
+// tables as launch_verify_recs reads them; the tile + tail launches over
+// device records (counted, hbec_verify_plan_stats); one verify call for a
+// stripe of the other route.  All queued on `stream`.
+struct VRec;
+struct VTile;
+struct VOther;
+void verify_tab(hbec_codec* codec, std::vector<uint32_t>& tab);
+int verify_recs_run(hbec_codec* codec, const VRec* d_recs, uint64_t n_recs, const VTile* d_tiles, uint64_t n_tiles,
+                    const uint32_t* d_tab, uint32_t* d_flags, hipStream_t stream, int max_blocks = 0);
+int verify_other_run(hbec_codec* codec, const VOther& o, uint32_t* d_flags, hipStream_t stream);
+
 struct URec;
 // out (^)= rows x in over unaligned-kernel records (any alignment, mixed
 // lengths), in launches of <= 4 outputs and <= kMaxK inputs (later input

@@ -5,10 +5,13 @@
 // S % 16 != 0 for 15 object sizes in 16; every object of an object plan with
 // k > 8) are coded by one more launch per pass of gf_apply_unaligned_plan over
 // their own records; stripe plans with k > 8 run the tiled kernel in
-// accumulate passes.
+// accumulate passes.  Verify of a plan (hbec_verify_plan) is read-only and
+// runs over the same tile records plus per-stripe records of its own
+// (vplan.h, vplan.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -19,6 +22,7 @@
 #include "gf256.h"
 #include "internal.h"
 #include "kernels.h"
+#include "vplan.h"
 
 using hbec::fail;
 using hbec::hip_fail;
@@ -51,6 +55,16 @@ struct hbec_plan {
     uint32_t* d_lists[hbec::kOddSpans] = {};
     hbec::OddStripeRecs orecs;
     std::unique_ptr<hbec::OddRecCache> rec_cache;
+    // Verify (hbec_verify_plan).  Every tile record carries its stripe's
+    // position in the caller's array (TileRec::pad_); the stripes without tile
+    // records, or of a shape gf_verify_tiles does not take, have a VRec and
+    // their {record, tile} list; `vother` are the stripes verified one by one.
+    uint64_t n_src = 0;  // entries of the caller's array (zero-length ones included)
+    hbec::VRec* d_vrecs = nullptr;
+    hbec::VTile* d_vtiles = nullptr;
+    uint32_t* d_vtab = nullptr;  // [k][vp_tab_stride(m)] parity coefficient tables
+    uint64_t n_vrecs = 0, n_vtiles = 0;
+    std::vector<hbec::VOther> vother;
 };
 
 // The gf_odd_rec records of a plan pass depend only on the plan's stripes and
@@ -246,7 +260,68 @@ int odd_stripe_rec_pass(int K, int R, int mode, const hbec::UPlanArgs& a, const 
     return HBEC_OK;
 }
 
+// The plan's Verify records and the codec's parity tables, to the device.
+int upload_verify(hbec_plan* p, hbec_codec* codec, hbec::VerifyRecs& vr) {
+    p->vother = std::move(vr.other);
+    if (vr.recs.empty()) return HBEC_OK;
+    std::vector<uint32_t> tab;
+    hbec::verify_tab(codec, tab);
+    int rc = upload(vr.recs, &p->d_vrecs, "plan verify records");
+    if (!rc) rc = upload(vr.tiles, &p->d_vtiles, "plan verify tile list");
+    if (!rc) rc = upload(tab, &p->d_vtab, "plan verify tables");
+    if (rc) return rc;
+    p->n_vrecs = vr.recs.size();
+    p->n_vtiles = vr.tiles.size();
+    return HBEC_OK;
+}
+
+std::atomic<uint64_t> g_vplan_launches{0}, g_vplan_per_stripe{0};
+
+int device_cus(int* cus) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute");
+    return HBEC_OK;
+}
+
 }  // namespace
+
+// ---- Verify over records (hbec_verify_plan, hbec_verify_host) ----
+
+void hbec::verify_tab(hbec_codec* codec, std::vector<uint32_t>& tab) {
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+    std::vector<uint8_t> mat((size_t)(k + m) * k);
+    hbec_matrix(codec, mat.data());
+    const uint32_t ts = hbec::vp_tab_stride(m);
+    tab.assign((size_t)k * ts, 0u);
+    for (int j = 0; j < k; ++j)
+        for (int r = 0; r < m; ++r) hbec::perm_table(mat[(size_t)(k + r) * k + j], tab.data() + (size_t)j * ts + 5 * r);
+}
+
+int hbec::verify_recs_run(hbec_codec* codec, const VRec* d_recs, uint64_t n_recs, const VTile* d_tiles,
+                          uint64_t n_tiles, const uint32_t* d_tab, uint32_t* d_flags, hipStream_t stream,
+                          int max_blocks) {
+    if (n_recs == 0) return HBEC_OK;
+    int cus = 0;
+    int rc = device_cus(&cus);
+    if (rc) return rc;
+    hipError_t e = hbec::launch_verify_recs(hbec_data_shards(codec), hbec_parity_shards(codec), d_recs, (uint32_t)n_recs,
+                                            d_tiles, (uint32_t)n_tiles, d_tab, d_flags, cus, stream, max_blocks);
+    if (e != hipSuccess) return hip_fail(e, "launch gf_verify_recs");
+    g_vplan_launches.fetch_add(n_tiles > 0 ? 2 : 1, std::memory_order_relaxed);  // tiles + byte tail
+    return HBEC_OK;
+}
+
+int hbec::verify_other_run(hbec_codec* codec, const VOther& o, uint32_t* d_flags, hipStream_t stream) {
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+    std::vector<hbec_view> v((size_t)k + m);
+    for (int j = 0; j < k; ++j) v[j] = {reinterpret_cast<void*>(o.a + (uint64_t)j * o.shard_len), 0};
+    for (int r = 0; r < m; ++r) v[(size_t)k + r] = {reinterpret_cast<void*>(o.b + (uint64_t)r * o.shard_len), 0};
+    g_vplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
+    return hbec_verify_batch(codec, v.data(), 1, o.shard_len, d_flags + o.idx, stream);
+}
 
 // out rows (^)= rows x in over unaligned-kernel records, in passes of <= 4
 // outputs x <= kMaxK inputs (later input passes accumulate).  sel_k > 0:
@@ -510,16 +585,24 @@ int hbec_plan_stripes(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n,
         p->k = k;
         p->m = m;
         p->tile_bytes = hbec::stripes_tile_bytes(std::min(k, hbec::kStripeMaxK));
+        if (n >= (1ull << 32)) return fail(HBEC_ERR_INVALID_ARG, "plan too large (>= 2^32 stripes)");
+        p->n_src = n;
         std::vector<hbec::TileRec> recs;
         std::vector<hbec::URec> urecs, erecs, brecs, orecs;
+        hbec::VerifyRecs vr;
         for (uint64_t i = 0; i < n; ++i) {
             const hbec_stripe& s = stripes[i];
             if (s.shard_len == 0) continue;
             if (!s.base) return fail(HBEC_ERR_INVALID_ARG, "stripe with null base");
             p->shard_bytes += s.shard_len;
+            const uint64_t sa = reinterpret_cast<uint64_t>(s.base);
             // (aligned stripes the record kernels code faster join them, hbec.cpp rec_route)
-            if (!aligned_stripe(s) ||
-                hbec::plan_rec_route(codec, s.shard_len, (reinterpret_cast<uintptr_t>(s.base) & 127u) == 0 && s.shard_len % 128 == 0)) {
+            const bool tiled = aligned_stripe(s) &&
+                               !hbec::plan_rec_route(codec, s.shard_len, (sa & 127u) == 0 && s.shard_len % 128 == 0);
+            if (m > 0 && !(tiled && hbec::vp_tiles_shape(k, m)) &&
+                !hbec::vp_add(vr, k, m, sa, sa + (uint64_t)k * s.shard_len, s.shard_len, i))
+                return fail(HBEC_ERR_INVALID_ARG, "plan too large (>= 2^31 tiles)");
+            if (!tiled) {
                 p->fallback.push_back(s);
                 add_urecs(urecs, erecs, brecs, orecs, s.base, nullptr, s.shard_len, k);
                 continue;
@@ -530,7 +613,7 @@ int hbec_plan_stripes(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n,
                 r.in_addr = r.out_addr = reinterpret_cast<uint64_t>(s.base) + off;
                 r.in_stride = r.out_stride = (uint32_t)s.shard_len;
                 r.valid = (uint32_t)std::min<uint64_t>((uint64_t)p->tile_bytes, s.shard_len - off);
-                r.pad_ = 0;
+                r.pad_ = (uint32_t)i;  // Verify: the flag of this tile's stripe
                 recs.push_back(r);
             }
         }
@@ -559,6 +642,7 @@ int hbec_plan_stripes(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n,
         if (!urc) urc = upload(brecs, &p->d_brecs, "plan large-shard records");
         if (!urc) urc = upload(orecs, &p->d_orecs, "plan stripe records");
         if (!urc) urc = build_tile_lists(p.get(), orecs);
+        if (!urc) urc = upload_verify(p.get(), codec, vr);
         if (urc) {
             hbec_plan_free(p.release());
             return urc;
@@ -584,8 +668,11 @@ int hbec_plan_objects(hbec_codec* codec, const hbec_object* objects, uint64_t n,
         p->m = m;
         p->objects = true;
         p->tile_bytes = hbec::stripes_tile_bytes(std::min(k, hbec::kStripeMaxK));
+        if (n >= (1ull << 32)) return fail(HBEC_ERR_INVALID_ARG, "plan too large (>= 2^32 objects)");
+        p->n_src = n;
         std::vector<hbec::TileRec> recs;
         std::vector<hbec::URec> urecs, erecs, brecs, orecs;
+        hbec::VerifyRecs vr;
         for (uint64_t i = 0; i < n; ++i) {
             const hbec_object& o = objects[i];
             if (o.shard_len == 0) continue;
@@ -593,7 +680,14 @@ int hbec_plan_objects(hbec_codec* codec, const hbec_object* objects, uint64_t n,
             p->shard_bytes += o.shard_len;
             const bool line = ((reinterpret_cast<uintptr_t>(o.data) | reinterpret_cast<uintptr_t>(o.parity)) & 127u) == 0 &&
                               o.shard_len % 128 == 0;
-            if (!aligned_object(o) || (k <= hbec::kStripeMaxK && hbec::plan_rec_route(codec, o.shard_len, line))) {
+            const bool to_recs =
+                !aligned_object(o) || (k <= hbec::kStripeMaxK && hbec::plan_rec_route(codec, o.shard_len, line));
+            // tile records exist for aligned objects of k <= 8 that stay off the record route
+            if (m > 0 && !(!to_recs && hbec::vp_tiles_shape(k, m)) &&
+                !hbec::vp_add(vr, k, m, reinterpret_cast<uint64_t>(o.data), reinterpret_cast<uint64_t>(o.parity),
+                              o.shard_len, i))
+                return fail(HBEC_ERR_INVALID_ARG, "plan too large (>= 2^31 tiles)");
+            if (to_recs) {
                 p->obj_fallback.push_back(o);
                 add_urecs(urecs, erecs, brecs, orecs, o.data, o.parity, o.shard_len, k);
                 continue;
@@ -611,7 +705,7 @@ int hbec_plan_objects(hbec_codec* codec, const hbec_object* objects, uint64_t n,
                 r.out_addr = reinterpret_cast<uint64_t>(o.parity) + off;
                 r.in_stride = r.out_stride = (uint32_t)o.shard_len;
                 r.valid = (uint32_t)std::min<uint64_t>((uint64_t)p->tile_bytes, o.shard_len - off);
-                r.pad_ = 0;
+                r.pad_ = (uint32_t)i;  // Verify: the flag of this tile's stripe
                 recs.push_back(r);
             }
         }
@@ -640,6 +734,7 @@ int hbec_plan_objects(hbec_codec* codec, const hbec_object* objects, uint64_t n,
         if (!urc) urc = upload(brecs, &p->d_brecs, "plan large-shard records");
         if (!urc) urc = upload(orecs, &p->d_orecs, "plan stripe records");
         if (!urc) urc = build_tile_lists(p.get(), orecs);
+        if (!urc) urc = upload_verify(p.get(), codec, vr);
         if (urc) {
             hbec_plan_free(p.release());
             return urc;
@@ -661,6 +756,9 @@ void hbec_plan_free(hbec_plan* plan) {
     if (plan->d_erecs) (void)hipFree(plan->d_erecs);
     if (plan->d_brecs) (void)hipFree(plan->d_brecs);
     if (plan->d_orecs) (void)hipFree(plan->d_orecs);
+    if (plan->d_vrecs) (void)hipFree(plan->d_vrecs);
+    if (plan->d_vtiles) (void)hipFree(plan->d_vtiles);
+    if (plan->d_vtab) (void)hipFree(plan->d_vtab);
     for (uint32_t* l : plan->d_lists)
         if (l) (void)hipFree(l);
     delete plan;
@@ -716,6 +814,52 @@ int hbec_reconstruct_plan(hbec_codec* codec, const hbec_plan* plan, const uint8_
         rows.resize((size_t)n_out * k);
         return run_plan(plan, surv, outs, rows, static_cast<hipStream_t>(hip_stream));
     });
+}
+
+int hbec_verify_plan(hbec_codec* codec, const hbec_plan* plan, uint32_t* d_flags, void* hip_stream) {
+    return hbec::guarded("hbec_verify_plan", [&]() -> int {
+        if (!codec || !plan || (!d_flags && plan->n_src)) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+        if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
+        if (m == 0 || plan->shard_bytes == 0) return HBEC_OK;
+        hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        if (plan->n_tiles > 0 && hbec::vp_tiles_shape(k, m)) {
+            // the aligned stripes' tile records (the other shapes have a VRec each)
+            std::vector<uint8_t> mat((size_t)(k + m) * k);
+            hbec_matrix(codec, mat.data());
+            hbec::VTileArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.n_tiles = (uint32_t)plan->n_tiles;
+            a.split = plan->objects ? 1u : 0u;
+            for (int r = 0; r < m; ++r)
+                for (int j = 0; j < k; ++j) hbec::perm_table(mat[(size_t)(k + r) * k + j], a.tab[r][j]);
+            int cus = 0;
+            int rc = device_cus(&cus);
+            if (rc) return rc;
+            hipError_t e = hbec::launch_verify_tiles(k, m, a, plan->d_tiles, d_flags, cus, stream);
+            if (e != hipSuccess) return hip_fail(e, "launch gf_verify_tiles");
+            g_vplan_launches.fetch_add(1, std::memory_order_relaxed);
+        }
+        int rc = hbec::verify_recs_run(codec, plan->d_vrecs, plan->n_vrecs, plan->d_vtiles, plan->n_vtiles,
+                                       plan->d_vtab, d_flags, stream);
+        for (size_t i = 0; i < plan->vother.size() && !rc; ++i)
+            rc = hbec::verify_other_run(codec, plan->vother[i], d_flags, stream);
+        return rc;
+    });
+}
+
+int hbec_verify_plan_stats(uint64_t* plan_launches, uint64_t* per_stripe_calls) {
+    return hbec::guarded("hbec_verify_plan_stats", [&]() -> int {
+        if (!plan_launches || !per_stripe_calls) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *plan_launches = g_vplan_launches.load(std::memory_order_relaxed);
+        *per_stripe_calls = g_vplan_per_stripe.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_verify_plan_tile_bytes(int k) {
+    (void)k;  // gf_verify_recs takes k at run time: one tile size
+    return (int)hbec::kVpTile;
 }
 
 }  // extern "C"

@@ -208,6 +208,15 @@ class Encoder:
     def EncodeStripes(self, stripes) -> None:
         check(N.lib().hbec_encode_host(self._h, self._stripes(stripes), len(stripes)))
 
+    def VerifyStripes(self, stripes) -> np.ndarray:
+        """Encoder.Verify of every host stripe (same argument forms as
+        EncodeStripes): a bool array, True where a stored parity shard differs
+        from the recomputed one (hbec_verify_host).  The stripes are only read."""
+        n = len(stripes)
+        out = np.zeros(max(n, 1), np.uint8)
+        check(N.lib().hbec_verify_host(self._h, self._stripes(stripes), n, out.ctypes.data_as(N._U8P)))
+        return out[:n].astype(bool)
+
     def EncodeStripesMD5(self, stripes):
         """EncodeStripes + the ShardHash of every shard of every stripe, hashed on
         the GPU (indexdb.go:746-753).  Returns [[hex] * (k+m)] per stripe."""

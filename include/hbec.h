@@ -288,6 +288,18 @@ int hbec_encode_plan(hbec_codec* codec, const hbec_plan* plan, void* hip_stream)
 /* Reconstruct every stripe with one erasure pattern (as hbec_reconstruct_batch). */
 int hbec_reconstruct_plan(hbec_codec* codec, const hbec_plan* plan, const uint8_t* present, int data_only,
                           void* hip_stream);
+/* Encoder.Verify of every stripe / object of the plan: d_flags[i] |= 1 when stripe i (its
+ * position in the array the plan was built from; n entries, device memory, caller-zeroed)
+ * has a stored parity shard that differs from the recomputed one.  Zero-length stripes are
+ * never flagged.  Read-only; queued on hip_stream, not waited for.  k <= 12 with m <= 4
+ * runs in at most three launches whatever the number of stripes; other shapes, and
+ * shards of 2^31 - 64 KiB bytes or more, take one hbec_verify_batch each.  d_flags may be
+ * NULL only for a plan built from no stripes. */
+int hbec_verify_plan(hbec_codec* codec, const hbec_plan* plan, uint32_t* d_flags, void* hip_stream);
+/* launches since load of the plan Verify kernels, and per-stripe verify calls of the other route */
+int hbec_verify_plan_stats(uint64_t* plan_launches, uint64_t* per_stripe_calls);
+/* shard bytes per wave tile of the any-alignment plan Verify kernel (k data shards) */
+int hbec_verify_plan_tile_bytes(int k);
 
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
@@ -314,6 +326,12 @@ void hbec_host_free(void* p);
 int hbec_host_device_addr(const void* p, uint64_t len, uint64_t* dev);
 int hbec_reconstruct_host(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n_stripes, const uint8_t* present,
                           int data_only);
+/* The same Verify as hbec_verify_plan for stripes in HOST memory (ecSplit layout); flags:
+ * n_stripes bytes (host), set to 0 / 1.  Synchronous.  Pinned, device-mapped stripes are
+ * read in place over PCIe; every other stripe is staged through a ring slot with one copy
+ * (a stripe larger than a slot in column pieces, its flag the OR over them).  Only the
+ * flags come back.  flags may be NULL only when n_stripes is 0. */
+int hbec_verify_host(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n_stripes, uint8_t* flags);
 /* Several GPUs from one process (a node's object server): the stripes are
  * cut into contiguous runs of about equal bytes, one per device, coded
  * concurrently by one host thread per device (each on its own ring /
