@@ -24,6 +24,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/hbec.h"
@@ -71,7 +72,13 @@ static const int g_grid_cap_env = (int)tune_knob("HBEC_GRID_CAP", 0);
 // work (the encode + ShardHash pipeline); 0 = none.
 thread_local int t_grid_cap = 0;
 void set_thread_grid_cap(int blocks) { t_grid_cap = blocks; }
-#define g_grid_cap (t_grid_cap > 0 ? (g_grid_cap_env > 0 ? std::min(t_grid_cap, g_grid_cap_env) : t_grid_cap) : g_grid_cap_env)
+// The thread's and the environment's cap (the smaller when both are set) on
+// the grid of an apply launch; Verify launches are never capped.
+static int apply_grid_cap(int grid) {
+    int cap = g_grid_cap_env;
+    if (t_grid_cap > 0) cap = cap > 0 ? std::min(t_grid_cap, cap) : t_grid_cap;
+    return cap > 0 ? std::min(grid, cap) : grid;
+}
 // Tiles per launch of the pipelined / packed kernels (HBEC_CHUNK_TILES):
 // a batch is split into launches of whole objects of at most this many
 // tiles.  Over one very long launch the blocks' grid-stride fronts drift
@@ -98,20 +105,16 @@ static const uint64_t g_vec_chunk_tiles = [] {
 // ---------------------------------------------------------------------------
 // Per-device facts (CU count, occupancy per kernel shape)
 // ---------------------------------------------------------------------------
+// the kernel families whose occupancy the launch paths ask for
+enum class OccKind { Unrolled, Pipelined, ForcedStream, Packed, Unaligned, VerifyPipe, VerifyPacked };
+
 struct DeviceInfo {
     int cus = 0;
-    std::map<std::pair<int, int>, int> blocks_per_cu;
+    std::map<std::tuple<OccKind, int, int>, int> blocks_per_cu;
 };
 
 static std::mutex g_dev_mu;
 static std::map<int, DeviceInfo> g_devs;
-
-// Occupancy ceiling of the verify kernel (for the tuning override).
-static int bpc_occ_cap(int k, int r) {
-    int b = 1;
-    if (verify_occupancy(k, r, &b) != hipSuccess) return 1;
-    return b;
-}
 
 static int current_device(int* dev) {
     hipError_t e = hipGetDevice(dev);
@@ -119,8 +122,8 @@ static int current_device(int* dev) {
     return HBEC_OK;
 }
 
-static int device_blocks(int dev, int k, int r, int pipe, int force_stream, int* cus, int* per_cu) {
-    std::lock_guard<std::mutex> g(g_dev_mu);
+// the device's entry with its CU count filled in; the caller holds g_dev_mu
+static int device_info(int dev, DeviceInfo** out) {
     DeviceInfo& d = g_devs[dev];
     if (d.cus == 0) {
         hipDeviceProp_t p;
@@ -128,39 +131,122 @@ static int device_blocks(int dev, int k, int r, int pipe, int force_stream, int*
         if (e != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
         d.cus = p.multiProcessorCount;
     }
-    // pipe: 1 = pipelined kernel, 2 = packed kernel (short shards), 3 = unaligned kernel
-    const int key_k = pipe == 3 ? 3000 : (force_stream ? -k : (pipe == 2 ? 2000 + k : (pipe ? 1000 + k : k)));
-    auto it = d.blocks_per_cu.find({key_k, r});
-    if (it == d.blocks_per_cu.end()) {
+    *out = &d;
+    return HBEC_OK;
+}
+
+int device_cus(int dev, int* cus) {
+    std::lock_guard<std::mutex> g(g_dev_mu);
+    DeviceInfo* d = nullptr;
+    int rc = device_info(dev, &d);
+    if (rc) return rc;
+    *cus = d->cus;
+    return HBEC_OK;
+}
+
+// CU count and resident blocks per CU (>= 1) of one kernel instance, queried
+// once per device and (kind, k, r); the unaligned kernels are keyed by r alone
+static int device_blocks(int dev, OccKind kind, int k, int r, int* cus, int* per_cu) {
+    std::lock_guard<std::mutex> g(g_dev_mu);
+    DeviceInfo* d = nullptr;
+    int rc = device_info(dev, &d);
+    if (rc) return rc;
+    if (kind == OccKind::Unaligned) k = 0;
+    auto it = d->blocks_per_cu.find({kind, k, r});
+    if (it == d->blocks_per_cu.end()) {
         int b = 0;
-        hipError_t e = pipe == 3   ? unaligned_occupancy(r, &b)
-                       : pipe == 2 ? packed_occupancy(k, r, &b)
-                                   : vec_occupancy(k, r, pipe, force_stream, &b);
+        hipError_t e = hipErrorInvalidValue;
+        switch (kind) {
+            case OccKind::Unrolled: e = vec_occupancy(k, r, 0, 0, &b); break;
+            case OccKind::Pipelined: e = vec_occupancy(k, r, 1, 0, &b); break;
+            case OccKind::ForcedStream: e = vec_occupancy(k, r, 0, 1, &b); break;
+            case OccKind::Packed: e = packed_occupancy(k, r, &b); break;
+            case OccKind::Unaligned: e = unaligned_occupancy(r, &b); break;
+            case OccKind::VerifyPipe: e = verify_occupancy(k, r, &b); break;
+            case OccKind::VerifyPacked: e = verify_packed_occupancy(k, r, &b); break;
+        }
         if (e != hipSuccess) return hip_fail(e, "occupancy query");
         if (b < 1) b = 1;
-        it = d.blocks_per_cu.emplace(std::make_pair(key_k, r), b).first;
+        it = d->blocks_per_cu.emplace(std::make_tuple(kind, k, r), b).first;
     }
-    *cus = d.cus;
+    *cus = d->cus;
     *per_cu = it->second;
     return HBEC_OK;
 }
+// the aligned strided kernel instance of a pass
+static OccKind vec_kind(int pipe, int force_stream) {
+    return force_stream ? OccKind::ForcedStream : (pipe ? OccKind::Pipelined : OccKind::Unrolled);
+}
+
+// ---------------------------------------------------------------------------
+// Pass arguments, object chunks and grids shared by the strided launch paths
+// ---------------------------------------------------------------------------
+// Rows [r0, r0 + R) x columns [c0, c0 + K) of `coeffs` (row-major, `ld` per
+// row; null: no tables) over in[c0..] and out[r0..]; every other field zero.
+static PassArgs make_pass(const hbec_view* in, const hbec_view* out, const uint8_t* coeffs, int ld, int r0, int R,
+                          int c0, int K, uint64_t shard_len) {
+    PassArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (int j = 0; j < K; ++j) {
+        a.in[j] = static_cast<const uint8_t*>(in[c0 + j].base);
+        a.in_stride[j] = in[c0 + j].obj_stride;
+    }
+    for (int r = 0; r < R; ++r) {
+        a.out[r] = static_cast<uint8_t*>(out[r0 + r].base);
+        a.out_stride[r] = out[r0 + r].obj_stride;
+        for (int j = 0; coeffs && j < K; ++j) perm_table(coeffs[(size_t)(r0 + r) * ld + c0 + j], a.tab[r][j]);
+    }
+    a.shard_len = shard_len;
+    return a;
+}
+
+// Objects per launch of a route whose objects take tpo tiles each: whole
+// objects, n_tiles < 2^31 and at most chunk_tiles per launch, at least one.
+static uint64_t objs_per_launch(uint64_t chunk_tiles, uint64_t tpo) {
+    return std::max<uint64_t>(1, std::min<uint64_t>(1ull << 31, chunk_tiles) / tpo);
+}
+static void set_tiles(PassArgs& b, uint64_t tpo) {
+    b.tiles_per_obj = (uint32_t)tpo;
+    b.n_tiles = (uint32_t)(b.n_obj * tpo);
+}
+// The packed routes (spo 16-B elements per object, te per wave tile, tiles
+// running across objects): n_elems < 2^31 and at most g_chunk_tiles tiles.
+static uint64_t packed_objs_per_launch(uint64_t spo, uint64_t te, uint64_t chunk_tiles) {
+    const uint64_t max_obj = std::max<uint64_t>(1, ((1ull << 31) - te) / spo);  // n_elems < 2^31
+    return std::min(max_obj, std::max<uint64_t>(1, chunk_tiles * te / spo));
+}
+static void set_packed_tiles(PassArgs& b, uint64_t spo, uint64_t te) {
+    b.elems_per_obj = (uint32_t)spo;
+    b.n_elems = (uint32_t)(b.n_obj * spo);
+    b.n_tiles = (uint32_t)((b.n_obj * spo + te - 1) / te);
+}
+
+// The K x R pass `a` over n_obj objects in launches of <= max_obj: fn(b, o0)
+// gets a copy of the pass whose bases are those of object o0 and whose n_obj
+// is the launch's, and returns an HBEC code.
+template <class Fn>
+static int for_object_chunks(const PassArgs& a, int K, int R, uint64_t n_obj, uint64_t max_obj, Fn fn) {
+    for (uint64_t o0 = 0; o0 < n_obj; o0 += max_obj) {
+        PassArgs b = a;
+        for (int j = 0; j < K; ++j) b.in[j] = a.in[j] + o0 * a.in_stride[j];
+        for (int r = 0; r < R; ++r) b.out[r] = a.out[r] + o0 * a.out_stride[r];
+        b.n_obj = std::min(max_obj, n_obj - o0);
+        const int rc = fn(b, o0);
+        if (rc) return rc;
+    }
+    return HBEC_OK;
+}
+
+// blocks of waves_per_block waves, one tile per wave at a time, within cap_blocks
+static int grid_blocks(uint64_t n_tiles, uint64_t waves_per_block, uint64_t cap_blocks) {
+    const uint64_t want = (n_tiles + waves_per_block - 1) / waves_per_block;
+    return (int)std::max<uint64_t>(1, std::min(want, cap_blocks));
+}
+static int launched(hipError_t e, const char* what) { return e == hipSuccess ? HBEC_OK : hip_fail(e, what); }
 
 // ---------------------------------------------------------------------------
 // Shards at any alignment (gf_odd, odd.hip)
 // ---------------------------------------------------------------------------
-static int cu_count(int dev, int* cus) {
-    std::lock_guard<std::mutex> g(g_dev_mu);
-    DeviceInfo& d = g_devs[dev];
-    if (d.cus == 0) {
-        hipDeviceProp_t p;
-        hipError_t e = hipGetDeviceProperties(&p, dev);
-        if (e != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
-        d.cus = p.multiProcessorCount;
-    }
-    *cus = d.cus;
-    return HBEC_OK;
-}
-
 // Per-object records of a strided record pass depend only on the views (bases
 // and strides), the object count, S and the pass shape, never on the data or
 // the coefficients.  Views coded again (a service reusing its batch buffers,
@@ -256,7 +342,7 @@ static int objrec_cached(const PassArgs& c, int K, int R, int m, int dev, uint64
 static int odd_launches(const PassArgs& a, int K, int R, int mode, bool accumulate, uint64_t n_obj,
                         uint64_t shard_len, uint32_t* flags, int dev, hipStream_t stream) {
     int cus = 0;
-    int rc = cu_count(dev, &cus);
+    int rc = device_cus(dev, &cus);
     if (rc) return rc;
     // the main kernel codes the guard band too (HBEC_ODD_EDGE_FUSE): one
     // apply launch group whose shards span >= 2 tiles (the edge tiles are
@@ -280,56 +366,43 @@ static int odd_launches(const PassArgs& a, int K, int R, int mode, bool accumula
             const int xs = odd_bp_schedule(K1, R, m, b.tab, false);
             const bool use_rec = xs >= 0 || ((m != 2 || K1 > 8) && odd_uses_records(K1, R));
             const uint64_t tpo = odd_tiles_per_obj(K1, m, shard_len, use_rec, xs);
-            const uint64_t max_obj = std::max<uint64_t>(1, std::min<uint64_t>((1ull << 31), odd_chunk_tiles()) / tpo);
+            const uint64_t max_obj = objs_per_launch(odd_chunk_tiles(), tpo);
             // per-object records of one launch's objects (stream-ordered
             // scratch of at most max_obj records, rebuilt per launch, freed
             // after the pass): device memory bounded by the chunk, not the batch
             uint32_t* recs = nullptr;  // scratch, allocated when a launch's records are not cached
             const uint64_t rw = odd_rec_words(K1, R, m);
-            for (uint64_t o0 = 0; o0 < n_obj; o0 += max_obj) {
-                const uint64_t no = std::min(max_obj, n_obj - o0);
-                PassArgs c = b;
-                for (int j = 0; j < K1; ++j) c.in[j] = b.in[j] + o0 * b.in_stride[j];
-                for (int r = 0; r < R; ++r) c.out[r] = b.out[r] + o0 * b.out_stride[r];
-                c.n_obj = no;
-                c.shard_len = shard_len;
+            b.shard_len = shard_len;
+            rc = for_object_chunks(b, K1, R, n_obj, max_obj, [&](PassArgs& c, uint64_t o0) {
                 uint32_t* lrecs = nullptr;
                 if (use_rec) {
-                    rc = objrec_cached(c, K1, R, m, dev, rw, stream, &lrecs);
-                    if (rc) {
-                        if (recs) scratch_free(recs, stream);
-                        return rc;
-                    }
+                    int lrc = objrec_cached(c, K1, R, m, dev, rw, stream, &lrecs);
+                    if (lrc) return lrc;
                     if (!lrecs) {
                         if (!recs) {
-                            rc = scratch_alloc(std::min(n_obj, max_obj) * rw * 4, stream, reinterpret_cast<void**>(&recs));
-                            if (rc) return rc;
+                            lrc = scratch_alloc(std::min(n_obj, max_obj) * rw * 4, stream, reinterpret_cast<void**>(&recs));
+                            if (lrc) {
+                                recs = nullptr;
+                                return lrc;
+                            }
                         }
-                        hipError_t e = launch_odd_objrec(K1, R, m, c, recs, stream);
-                        if (e != hipSuccess) {
-                            scratch_free(recs, stream);
-                            return hip_fail(e, "launch gf_odd_objrec");
-                        }
+                        lrc = launched(launch_odd_objrec(K1, R, m, c, recs, stream), "launch gf_odd_objrec");
+                        if (lrc) return lrc;
                         lrecs = recs;
                     }
                 }
-                c.tiles_per_obj = (uint32_t)tpo;
-                c.n_tiles = (uint32_t)(no * tpo);
+                set_tiles(c, tpo);
                 c.fuse = odd_edge_fuse(K1, R, m, use_rec, xs, false, shard_len) && K <= kOddMaxK && tpo >= 2 &&
                                  shard_len < (1ull << 30) ? 1u : 0u;
                 fused = c.fuse != 0u;
-                const uint64_t wpb = odd_waves_per_block(xs);
-                const uint64_t want = (c.n_tiles + wpb - 1) / wpb;
                 const uint64_t cap = (uint64_t)cus * (uint64_t)odd_blocks_per_cu(m, K1, R, false, use_rec, xs);
-                int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, cap));
-                if (g_grid_cap > 0) grid = std::min(grid, g_grid_cap);
-                hipError_t e = launch_odd(K1, R, m, c, flags ? flags + o0 : nullptr, lrecs, grid, stream, xs);
-                if (e != hipSuccess) {
-                    if (recs) scratch_free(recs, stream);
-                    return hip_fail(e, "launch gf_odd");
-                }
-            }
+                // the one route whose Verify launches (mode 2) take the grid cap too
+                const int grid = apply_grid_cap(grid_blocks(c.n_tiles, odd_waves_per_block(xs), cap));
+                return launched(launch_odd(K1, R, m, c, flags ? flags + o0 : nullptr, lrecs, grid, stream, xs),
+                                "launch gf_odd");
+            });
             if (recs) scratch_free(recs, stream);
+            if (rc) return rc;
         }
     }
     // the guard-band bytes of every shard, all K inputs of the pass at once
@@ -343,11 +416,6 @@ static int odd_launches(const PassArgs& a, int K, int R, int mode, bool accumula
     hipError_t e = launch_odd_edges(K, R, mode == 2 ? 2 : (accumulate ? 1 : 0), g, flags, stream);
     if (e != hipSuccess) return hip_fail(e, "launch gf_odd_edges");
     return HBEC_OK;
-}
-
-static int apply_odd(const PassArgs& a, int K, int R, bool accumulate, uint64_t n_obj, uint64_t shard_len, int dev,
-                     hipStream_t stream) {
-    return odd_launches(a, K, R, 0, accumulate, n_obj, shard_len, nullptr, dev, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -376,14 +444,14 @@ bool rec_route(int cols, int rows, uint64_t shard_len, bool line_aligned, bool b
     return shard_len >= HBEC_REC_ROUTE_MIN_S && (!line_aligned || r >= 4) && (cols * r <= 24 || bitplane);
 }
 // the first pass's rows (<= kMaxR of `rows`, coefficients row-major with
-// `cols` per row) have a compiled bit-plane schedule
-static bool bitplane_rows(int k, int rows, const uint8_t* coeffs, int cols, bool plan) {
+// `cols` per row) have a compiled bit-plane schedule (mode 0 apply, 2 Verify)
+static bool bitplane_rows(int k, int rows, const uint8_t* coeffs, int cols, int mode, bool plan) {
     if (k > kMaxK) return false;
     uint32_t tab[kMaxR][kMaxK][5] = {};
     const int r = std::min(rows, kMaxR);
     for (int q = 0; q < r; ++q)
         for (int j = 0; j < k; ++j) tab[q][j][0] = (uint32_t)coeffs[(size_t)q * cols + j] << 8;  // byte 1 = c * 1
-    return odd_bp_schedule(k, r, 0, tab, plan) >= 0;
+    return odd_bp_schedule(k, r, mode, tab, plan) >= 0;
 }
 static bool line_aligned(const void* p, uint64_t stride) {
     return (reinterpret_cast<uintptr_t>(p) & 127u) == 0 && stride % 128 == 0;
@@ -404,7 +472,7 @@ int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, 
     for (int r = 0; r < rows && line; ++r) line = line_aligned(out[r].base, out[r].obj_stride);
     // the schedule match only where it can change the route (rec_route with and without it differ)
     const bool to_rec = vec && rec_route(cols, rows, shard_len, line, true) &&
-                        (rec_route(cols, rows, shard_len, line, false) || bitplane_rows(cols, rows, coeffs, cols, false));
+                        (rec_route(cols, rows, shard_len, line, false) || bitplane_rows(cols, rows, coeffs, cols, 0, false));
     for (int c = 0; c < cols; ++c)
         if (!in[c].base) return fail(HBEC_ERR_INVALID_ARG, "apply: null input view");
     for (int r = 0; r < rows; ++r)
@@ -422,102 +490,56 @@ int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, 
         const int R = std::min(kMaxR, rows - r0);
         for (int c0 = 0; c0 < cols; c0 += kMaxK) {
             const int K = std::min(kMaxK, cols - c0);
-            PassArgs a;
-            std::memset(&a, 0, sizeof(a));
-            for (int j = 0; j < K; ++j) {
-                a.in[j] = static_cast<const uint8_t*>(in[c0 + j].base);
-                a.in_stride[j] = in[c0 + j].obj_stride;
-            }
-            for (int r = 0; r < R; ++r) {
-                a.out[r] = static_cast<uint8_t*>(out[r0 + r].base);
-                a.out_stride[r] = out[r0 + r].obj_stride;
-                for (int j = 0; j < K; ++j) perm_table(coeffs[(size_t)(r0 + r) * cols + c0 + j], a.tab[r][j]);
-            }
-            a.shard_len = shard_len;
+            PassArgs a = make_pass(in, out, coeffs, cols, r0, R, c0, K, shard_len);
             a.accumulate = c0 > 0 ? 1u : 0u;
+            int cus = 0, per_cu = 0;
             if (vec && is_packed_shape(K, R, shard_len, c0 > 0, force_stream)) {
                 // short shards: wave tiles across objects (gf_apply_packed)
-                int cus = 0, per_cu = 0;
-                rc = device_blocks(dev, K, R, 2, 0, &cus, &per_cu);
+                rc = device_blocks(dev, OccKind::Packed, K, R, &cus, &per_cu);
                 if (rc) return rc;
+                if (g_blocks_per_cu_override > 0) per_cu = g_blocks_per_cu_override;
                 const uint64_t spo = shard_len / 16;
                 const uint64_t te = (uint64_t)packed_tile_elems(K);
-                uint64_t max_obj = std::max<uint64_t>(1, ((1ull << 31) - te) / spo);  // n_elems < 2^31
-                max_obj = std::min(max_obj, std::max<uint64_t>(1, g_chunk_tiles * te / spo));
-                for (uint64_t o0 = 0; o0 < n_obj; o0 += max_obj) {
-                    const uint64_t no = std::min(max_obj, n_obj - o0);
-                    PassArgs b = a;
-                    for (int j = 0; j < K; ++j) b.in[j] = a.in[j] + o0 * a.in_stride[j];
-                    for (int r = 0; r < R; ++r) b.out[r] = a.out[r] + o0 * a.out_stride[r];
-                    b.n_obj = no;
-                    b.elems_per_obj = (uint32_t)spo;
-                    b.n_elems = (uint32_t)(no * spo);
-                    b.n_tiles = (uint32_t)((no * spo + te - 1) / te);
-                    const uint64_t wpb = (uint64_t)kPipeBlockThreads / 64;
-                    const uint64_t want_blocks = (b.n_tiles + wpb - 1) / wpb;
-                    const uint64_t cap = (uint64_t)cus * (uint64_t)(g_blocks_per_cu_override > 0
-                                                                         ? g_blocks_per_cu_override
-                                                                         : per_cu);
-                    int grid = (int)std::max<uint64_t>(1, std::min(want_blocks, cap));
-                    if (g_grid_cap > 0) grid = std::min(grid, g_grid_cap);
-                    hipError_t e = launch_packed(K, R, b, grid, stream);
-                    if (e != hipSuccess) return hip_fail(e, "launch gf_apply_packed");
-                }
+                const uint64_t max_obj = packed_objs_per_launch(spo, te, g_chunk_tiles);
+                rc = for_object_chunks(a, K, R, n_obj, max_obj, [&](PassArgs& b, uint64_t) {
+                    set_packed_tiles(b, spo, te);
+                    const int grid = grid_blocks(b.n_tiles, kPipeBlockThreads / 64, (uint64_t)cus * per_cu);
+                    return launched(launch_packed(K, R, b, apply_grid_cap(grid), stream), "launch gf_apply_packed");
+                });
             } else if (vec && !to_rec) {
-                int cus = 0, per_cu = 0;
-                rc = device_blocks(dev, K, R, is_pipe_shape(K, R, shard_len, force_stream) && c0 == 0, force_stream,
-                                   &cus, &per_cu);
+                // the pipelined instance's occupancy only for the first column pass
+                const int pipe = is_pipe_shape(K, R, shard_len, force_stream) && c0 == 0;
+                rc = device_blocks(dev, vec_kind(pipe, force_stream), K, R, &cus, &per_cu);
                 if (rc) return rc;
+                if (g_blocks_per_cu_override > 0) per_cu = g_blocks_per_cu_override;
                 const uint64_t tile = (uint64_t)vec_tile_bytes(K, R, shard_len, c0 > 0, force_stream);
                 const uint64_t tpo = (shard_len + tile - 1) / tile;
+                const uint64_t wpb = (uint64_t)vec_block_threads(K, R, shard_len, c0 > 0, force_stream) / 64;
                 // keep n_tiles < 2^31 (and <= g_vec_chunk_tiles) per launch: split the batch by objects
-                const uint64_t max_obj = std::max<uint64_t>(1, std::min<uint64_t>((1ull << 31), g_vec_chunk_tiles) / tpo);
-                for (uint64_t o0 = 0; o0 < n_obj; o0 += max_obj) {
-                    const uint64_t no = std::min(max_obj, n_obj - o0);
-                    PassArgs b = a;
-                    for (int j = 0; j < K; ++j) b.in[j] = a.in[j] + o0 * a.in_stride[j];
-                    for (int r = 0; r < R; ++r) b.out[r] = a.out[r] + o0 * a.out_stride[r];
-                    b.n_obj = no;
-                    b.tiles_per_obj = (uint32_t)tpo;
-                    b.n_tiles = (uint32_t)(no * tpo);
-                    const uint64_t wpb = (uint64_t)vec_block_threads(K, R, shard_len, c0 > 0, force_stream) / 64;
-                    const uint64_t want_blocks = (b.n_tiles + wpb - 1) / wpb;
-                    const uint64_t cap = (uint64_t)cus * (uint64_t)(g_blocks_per_cu_override > 0
-                                                                         ? g_blocks_per_cu_override
-                                                                         : per_cu);
-                    int grid = (int)std::max<uint64_t>(1, std::min(want_blocks, cap));
-                    if (g_grid_cap > 0) grid = std::min(grid, g_grid_cap);
-                    hipError_t e = launch_vec(K, R, b, grid, stream, force_stream);
-                    if (e != hipSuccess) return hip_fail(e, "launch gf_apply_vec");
-                }
+                const uint64_t max_obj = objs_per_launch(g_vec_chunk_tiles, tpo);
+                rc = for_object_chunks(a, K, R, n_obj, max_obj, [&](PassArgs& b, uint64_t) {
+                    set_tiles(b, tpo);
+                    const int grid = grid_blocks(b.n_tiles, wpb, (uint64_t)cus * per_cu);
+                    return launched(launch_vec(K, R, b, apply_grid_cap(grid), stream, force_stream), "launch gf_apply_vec");
+                });
             } else if (odd_enabled() && cols <= kOddMaxK && pos32_shard(shard_len)) {
                 // any alignment / length: gf_odd (odd.hip), passes of <= 8 inputs,
                 // later ones accumulating into the outputs
-                rc = apply_odd(a, K, R, c0 > 0, n_obj, shard_len, dev, stream);
-                if (rc) return rc;
+                rc = odd_launches(a, K, R, 0, c0 > 0, n_obj, shard_len, nullptr, dev, stream);
             } else {
                 // any alignment: aligned 16-B accesses with in-register shifts (gf_apply_unaligned)
-                int cus = 0, per_cu = 0;
-                rc = device_blocks(dev, K, R, 3, 0, &cus, &per_cu);
+                rc = device_blocks(dev, OccKind::Unaligned, K, R, &cus, &per_cu);
                 if (rc) return rc;
                 if (g_unaligned_bpc > 0) per_cu = std::min(per_cu, g_unaligned_bpc);
                 const uint64_t tpo = unaligned_tiles_per_obj(shard_len);
-                const uint64_t max_obj = std::max<uint64_t>(1, std::min<uint64_t>((1ull << 31), g_chunk_tiles) / tpo);
-                for (uint64_t o0 = 0; o0 < n_obj; o0 += max_obj) {
-                    const uint64_t no = std::min(max_obj, n_obj - o0);
-                    PassArgs b = a;
-                    for (int j = 0; j < K; ++j) b.in[j] = a.in[j] + o0 * a.in_stride[j];
-                    for (int r = 0; r < R; ++r) b.out[r] = a.out[r] + o0 * a.out_stride[r];
-                    b.n_obj = no;
-                    b.tiles_per_obj = (uint32_t)tpo;
-                    b.n_tiles = (uint32_t)(no * tpo);
-                    const uint64_t want_blocks = (b.n_tiles + kBlockThreads / 64 - 1) / (kBlockThreads / 64);
-                    int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(want_blocks, (uint64_t)cus * per_cu));
-                    if (g_grid_cap > 0) grid = std::min(grid, g_grid_cap);
-                    hipError_t e = launch_unaligned(K, R, b, grid, stream);
-                    if (e != hipSuccess) return hip_fail(e, "launch gf_apply_unaligned");
-                }
+                const uint64_t max_obj = objs_per_launch(g_chunk_tiles, tpo);
+                rc = for_object_chunks(a, K, R, n_obj, max_obj, [&](PassArgs& b, uint64_t) {
+                    set_tiles(b, tpo);
+                    const int grid = grid_blocks(b.n_tiles, kBlockThreads / 64, (uint64_t)cus * per_cu);
+                    return launched(launch_unaligned(K, R, b, apply_grid_cap(grid), stream), "launch gf_apply_unaligned");
+                });
             }
+            if (rc) return rc;
         }
     }
     return HBEC_OK;
@@ -1012,7 +1034,7 @@ static int mixed_fast(const hbec_codec* c, const hbec_view* views, std::vector<M
     int dev = 0, cus = 0;
     int rc = current_device(&dev);
     if (rc) return rc;
-    rc = cu_count(dev, &cus);
+    rc = device_cus(dev, &cus);
     if (rc) return rc;
     const size_t rec_bytes = recs.size() * sizeof(MixedRec), ent_bytes = ents.size() * sizeof(MixedEnt);
     void* d = nullptr;
@@ -1039,7 +1061,7 @@ static int mixed_fast(const hbec_codec* c, const hbec_view* views, std::vector<M
             a.tiles_per_obj = (uint32_t)tpo;
             a.shard_len = (uint32_t)shard_len;
             int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((a.n_tiles + wpb - 1) / wpb, (uint64_t)cus));
-            if (g_grid_cap > 0) grid = std::min(grid, g_grid_cap);
+            grid = apply_grid_cap(grid);
             const uint64_t waves = (uint64_t)grid * wpb;
             a.iters = (uint32_t)((a.n_tiles + waves - 1) / waves);
             // the entries are sorted by record and every record is used
@@ -1141,7 +1163,7 @@ int hbec_new(int data_shards, int parity_shards, hbec_codec** out) {
         c->k = data_shards;
         c->m = parity_shards;
         if (!build_matrix(c->k, c->m, c->matrix)) return fail(HBEC_ERR_SINGULAR, "matrix is singular");
-        c->bp_plan = c->m > 0 && hbec::bitplane_rows(c->k, c->m, c->matrix.data() + (size_t)c->k * c->k, c->k, true);
+        c->bp_plan = c->m > 0 && hbec::bitplane_rows(c->k, c->m, c->matrix.data() + (size_t)c->k * c->k, c->k, 0, true);
         *out = c.release();
         return HBEC_OK;
     });
@@ -1385,7 +1407,7 @@ static int wide_grid(uint64_t n_tiles, int dflt) {
     static const int env = (int)tune_knob("HBEC_WIDE_BPC", 0);
     const int bpc = env > 0 ? env : dflt;
     int dev = 0, cus = 256;
-    if (current_device(&dev) == HBEC_OK) (void)cu_count(dev, &cus);
+    if (current_device(&dev) == HBEC_OK) (void)device_cus(dev, &cus);
     return (int)std::max<uint64_t>(1, std::min<uint64_t>((n_tiles + 3) / 4, (uint64_t)cus * bpc));
 }
 
@@ -1409,10 +1431,6 @@ static int apply_wide(int rows, int cols, const uint8_t* coeffs, const hbec_view
                          });
 }
 
-}  // namespace hbec
-
-extern "C" {
-
 static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, uint64_t shard_len, uint32_t* flags,
                         hipStream_t stream) {
     const int k = c->k, m = c->m;
@@ -1420,51 +1438,23 @@ static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, u
     bool vec = vec_len(shard_len);
     for (int i = 0; i < k + m && vec; ++i) vec = aligned16(views[i].base) && vec_len(views[i].obj_stride);
     const uint8_t* prow = c->matrix.data() + (size_t)k * k;
+    int dev = 0, cus = 0, bpc = 1;
+    int rc = current_device(&dev);
+    if (rc) return rc;
     if (vec && is_verify_packed_shape(k, m, shard_len)) {
         // short shards: wave tiles across objects (gf_verify_packed)
-        PassArgs a;
-        std::memset(&a, 0, sizeof(a));
-        for (int j = 0; j < k; ++j) {
-            a.in[j] = static_cast<const uint8_t*>(views[j].base);
-            a.in_stride[j] = views[j].obj_stride;
-        }
-        for (int r = 0; r < m; ++r) {
-            a.out[r] = static_cast<uint8_t*>(views[k + r].base);
-            a.out_stride[r] = views[k + r].obj_stride;
-            for (int j = 0; j < k; ++j) perm_table(prow[(size_t)r * k + j], a.tab[r][j]);
-        }
-        a.shard_len = shard_len;
-        int dev = 0, cus = 0, bpc = 1;
-        int rc = current_device(&dev);
+        const PassArgs a = make_pass(views, views + k, prow, k, 0, m, 0, k, shard_len);
+        rc = device_blocks(dev, OccKind::VerifyPacked, k, m, &cus, &bpc);
         if (rc) return rc;
-        hipDeviceProp_t p;
-        hipError_t e = hipGetDeviceProperties(&p, dev);
-        if (e != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
-        cus = p.multiProcessorCount;
-        e = verify_packed_occupancy(k, m, &bpc);
-        if (e != hipSuccess) return hip_fail(e, "verify occupancy");
-        bpc = std::max(1, bpc);
         if (g_blocks_per_cu_override > 0) bpc = g_blocks_per_cu_override;
         const uint64_t spo = shard_len / 16;
         const uint64_t te = (uint64_t)verify_packed_tile_elems(k);
-        uint64_t max_obj = std::max<uint64_t>(1, ((1ull << 31) - te) / spo);  // n_elems < 2^31
-        max_obj = std::min(max_obj, std::max<uint64_t>(1, g_chunk_tiles * te / spo));
-        for (uint64_t o0 = 0; o0 < n_obj; o0 += max_obj) {
-            const uint64_t no = std::min(max_obj, n_obj - o0);
-            PassArgs b = a;
-            for (int j = 0; j < k; ++j) b.in[j] = a.in[j] + o0 * a.in_stride[j];
-            for (int r = 0; r < m; ++r) b.out[r] = a.out[r] + o0 * a.out_stride[r];
-            b.n_obj = no;
-            b.elems_per_obj = (uint32_t)spo;
-            b.n_elems = (uint32_t)(no * spo);
-            b.n_tiles = (uint32_t)((no * spo + te - 1) / te);
-            const uint64_t wpb = (uint64_t)kPipeBlockThreads / 64;
-            const uint64_t want = (b.n_tiles + wpb - 1) / wpb;
-            const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)cus * bpc));
-            e = launch_verify_packed(k, m, b, flags + o0, grid, stream);
-            if (e != hipSuccess) return hip_fail(e, "launch gf_verify_packed");
-        }
-        return HBEC_OK;
+        const uint64_t max_obj = packed_objs_per_launch(spo, te, g_chunk_tiles);
+        return for_object_chunks(a, k, m, n_obj, max_obj, [&](PassArgs& b, uint64_t o0) {
+            set_packed_tiles(b, spo, te);
+            const int grid = grid_blocks(b.n_tiles, kPipeBlockThreads / 64, (uint64_t)cus * bpc);
+            return launched(launch_verify_packed(k, m, b, flags + o0, grid, stream), "launch gf_verify_packed");
+        });
     }
     // 16-B-aligned Verify stays on gf_verify_pipe (2-4 points ahead of the
     // record kernels from 5+3 to 8+3 at any pitch) except where its tables
@@ -1472,57 +1462,24 @@ static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, u
     // (8+4: 59.8-62.1 -> 74.3-75.5 %, profiles/r05_ab_route.jsonl r5_vroute).
     // Tuning builds: HBEC_VERIFY_ROUTE=0 keeps them all there.
     static const bool verify_route = tune_knob("HBEC_VERIFY_ROUTE", 1) != 0;
-    bool v_to_rec = vec && verify_route && odd_enabled() && k >= 5 && k <= 8 && m <= kMaxR && k * m > 24 &&
-                    shard_len >= HBEC_REC_ROUTE_MIN_S && pos32_shard(shard_len);
-    if (v_to_rec) {
-        uint32_t tab[kMaxR][kMaxK][5] = {};
-        for (int r = 0; r < m; ++r)
-            for (int j = 0; j < k; ++j) tab[r][j][0] = (uint32_t)prow[(size_t)r * k + j] << 8;  // byte 1 = c * 1
-        v_to_rec = odd_bp_schedule(k, m, 2, tab, false) >= 0;
-    }
+    const bool v_to_rec = vec && verify_route && odd_enabled() && k >= 5 && k <= 8 && m <= kMaxR && k * m > 24 &&
+                          shard_len >= HBEC_REC_ROUTE_MIN_S && pos32_shard(shard_len) &&
+                          bitplane_rows(k, m, prow, k, 2, false);
     if (vec && verify_supported(k, m) && !v_to_rec) {
-        PassArgs a;
-        std::memset(&a, 0, sizeof(a));
-        for (int j = 0; j < k; ++j) {
-            a.in[j] = static_cast<const uint8_t*>(views[j].base);
-            a.in_stride[j] = views[j].obj_stride;
-        }
-        for (int r = 0; r < m; ++r) {
-            a.out[r] = static_cast<uint8_t*>(views[k + r].base);
-            a.out_stride[r] = views[k + r].obj_stride;
-            for (int j = 0; j < k; ++j) perm_table(prow[(size_t)r * k + j], a.tab[r][j]);
-        }
-        a.shard_len = shard_len;
+        const PassArgs a = make_pass(views, views + k, prow, k, 0, m, 0, k, shard_len);
         const uint64_t tile = (uint64_t)verify_tile_bytes(k);
         const uint64_t tpo = (shard_len + tile - 1) / tile;
-        int dev = 0, cus = 0, bpc = 1;
-        int rc = current_device(&dev);
+        rc = device_blocks(dev, OccKind::VerifyPipe, k, m, &cus, &bpc);
         if (rc) return rc;
-        {
-            hipDeviceProp_t p;
-            hipError_t e = hipGetDeviceProperties(&p, dev);
-            if (e != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
-            cus = p.multiProcessorCount;
-            e = verify_occupancy(k, m, &bpc);
-            if (e != hipSuccess) return hip_fail(e, "verify occupancy");
-            bpc = std::max(1, kPipeBlocksPerCu > 0 ? std::min(bpc, kPipeBlocksPerCu) : bpc);
-            if (g_blocks_per_cu_override > 0) bpc = std::min(std::max(1, bpc_occ_cap(k, m)), g_blocks_per_cu_override);
-        }
-        const uint64_t max_obj = std::max<uint64_t>(1, (1ull << 31) / tpo);
-        for (uint64_t o0 = 0; o0 < n_obj; o0 += max_obj) {
-            const uint64_t no = std::min(max_obj, n_obj - o0);
-            PassArgs b = a;
-            for (int j = 0; j < k; ++j) b.in[j] = a.in[j] + o0 * a.in_stride[j];
-            for (int r = 0; r < m; ++r) b.out[r] = a.out[r] + o0 * a.out_stride[r];
-            b.n_obj = no;
-            b.tiles_per_obj = (uint32_t)tpo;
-            b.n_tiles = (uint32_t)(no * tpo);
-            const uint64_t want = (b.n_tiles + 3) / 4;
-            const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)cus * bpc));
-            hipError_t e = launch_verify(k, m, b, flags + o0, grid, stream);
-            if (e != hipSuccess) return hip_fail(e, "launch gf_verify_pipe");
-        }
-        return HBEC_OK;
+        // a tuning build's HBEC_BLOCKS_PER_CU: within the occupancy, past the pipelined kernels' clamp
+        if (g_blocks_per_cu_override > 0) bpc = std::min(bpc, g_blocks_per_cu_override);
+        else if (kPipeBlocksPerCu > 0) bpc = std::min(bpc, kPipeBlocksPerCu);
+        // n_tiles < 2^31 per launch only: no chunk limit on this route
+        return for_object_chunks(a, k, m, n_obj, objs_per_launch(1ull << 31, tpo), [&](PassArgs& b, uint64_t o0) {
+            set_tiles(b, tpo);
+            const int grid = grid_blocks(b.n_tiles, 4, (uint64_t)cus * bpc);
+            return launched(launch_verify(k, m, b, flags + o0, grid, stream), "launch gf_verify_pipe");
+        });
     }
     // k <= 8: gf_odd verify; 9 <= k <= 12 with 3 or 4 parity rows: the record
     // kernel with LDS tables in one pass (10+4 54.1 -> 64.5 %, 12+4 45.7 ->
@@ -1541,23 +1498,10 @@ static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, u
     }
     if (odd_enabled() && odd_verify && pos32_shard(shard_len)) {
         // any alignment: recompute and compare in one pass (gf_odd verify), <= 4 rows per launch
-        int dev = 0;
-        int rc = current_device(&dev);
-        if (rc) return rc;
         for (int r0 = 0; r0 < m; r0 += kMaxR) {
             const int R = std::min(kMaxR, m - r0);
-            PassArgs a;
-            std::memset(&a, 0, sizeof(a));
-            for (int j = 0; j < k; ++j) {
-                a.in[j] = static_cast<const uint8_t*>(views[j].base);
-                a.in_stride[j] = views[j].obj_stride;
-            }
-            for (int r = 0; r < R; ++r) {
-                a.out[r] = static_cast<uint8_t*>(views[k + r0 + r].base);
-                a.out_stride[r] = views[k + r0 + r].obj_stride;
-                for (int j = 0; j < k; ++j) perm_table(prow[(size_t)(r0 + r) * k + j], a.tab[r][j]);
-            }
-            rc = odd_launches(a, k, R, 2, false, n_obj, shard_len, flags, dev, stream);
+            rc = odd_launches(make_pass(views, views + k, prow, k, r0, R, 0, k, shard_len), k, R, 2, false, n_obj,
+                              shard_len, flags, dev, stream);
             if (rc) return rc;
         }
         return HBEC_OK;
@@ -1569,42 +1513,19 @@ static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, u
     }
     if (k <= kMaxK) {
         // any alignment: recompute and compare in one pass (gf_verify_unaligned), <= 4 rows per launch
-        int dev = 0, cus = 0;
-        int rc = current_device(&dev);
-        if (rc) return rc;
         const uint64_t tpo = unaligned_tiles_per_obj(shard_len);
-        const uint64_t max_obj = std::max<uint64_t>(1, std::min<uint64_t>((1ull << 31), g_chunk_tiles) / tpo);
         for (int r0 = 0; r0 < m; r0 += kMaxR) {
             const int R = std::min(kMaxR, m - r0);
-            int per_cu = 0;
-            rc = device_blocks(dev, k, R, 3, 0, &cus, &per_cu);
+            rc = device_blocks(dev, OccKind::Unaligned, k, R, &cus, &bpc);
             if (rc) return rc;
-            if (g_unaligned_bpc > 0) per_cu = std::min(per_cu, g_unaligned_bpc);
-            PassArgs a;
-            std::memset(&a, 0, sizeof(a));
-            for (int j = 0; j < k; ++j) {
-                a.in[j] = static_cast<const uint8_t*>(views[j].base);
-                a.in_stride[j] = views[j].obj_stride;
-            }
-            for (int r = 0; r < R; ++r) {
-                a.out[r] = static_cast<uint8_t*>(views[k + r0 + r].base);
-                a.out_stride[r] = views[k + r0 + r].obj_stride;
-                for (int j = 0; j < k; ++j) perm_table(prow[(size_t)(r0 + r) * k + j], a.tab[r][j]);
-            }
-            a.shard_len = shard_len;
-            for (uint64_t o0 = 0; o0 < n_obj; o0 += max_obj) {
-                const uint64_t no = std::min(max_obj, n_obj - o0);
-                PassArgs b = a;
-                for (int j = 0; j < k; ++j) b.in[j] = a.in[j] + o0 * a.in_stride[j];
-                for (int r = 0; r < R; ++r) b.out[r] = a.out[r] + o0 * a.out_stride[r];
-                b.n_obj = no;
-                b.tiles_per_obj = (uint32_t)tpo;
-                b.n_tiles = (uint32_t)(no * tpo);
-                const uint64_t want = (b.n_tiles + kBlockThreads / 64 - 1) / (kBlockThreads / 64);
-                const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)cus * per_cu));
-                hipError_t e = launch_verify_unaligned(k, R, b, flags + o0, grid, stream);
-                if (e != hipSuccess) return hip_fail(e, "launch gf_verify_unaligned");
-            }
+            if (g_unaligned_bpc > 0) bpc = std::min(bpc, g_unaligned_bpc);
+            const PassArgs a = make_pass(views, views + k, prow, k, r0, R, 0, k, shard_len);
+            rc = for_object_chunks(a, k, R, n_obj, objs_per_launch(g_chunk_tiles, tpo), [&](PassArgs& b, uint64_t o0) {
+                set_tiles(b, tpo);
+                const int grid = grid_blocks(b.n_tiles, kBlockThreads / 64, (uint64_t)cus * bpc);
+                return launched(launch_verify_unaligned(k, R, b, flags + o0, grid, stream), "launch gf_verify_unaligned");
+            });
+            if (rc) return rc;
         }
         return HBEC_OK;
     }
@@ -1615,29 +1536,24 @@ static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, u
     if (e != hipSuccess) return hip_fail(e, "hipMallocAsync verify scratch");
     std::vector<hbec_view> out(m);
     for (int r = 0; r < m; ++r) out[r] = {scratch + (size_t)r * shard_len, (uint64_t)m * shard_len};
-    int rc = apply_views(m, k, prow, views, out.data(), n_obj, shard_len, stream);
+    rc = apply_views(m, k, prow, views, out.data(), n_obj, shard_len, stream);
     for (int r0 = 0; r0 < m && rc == HBEC_OK; r0 += kMaxR) {
         const int R = std::min(kMaxR, m - r0);
-        PassArgs a;
-        std::memset(&a, 0, sizeof(a));
-        for (int r = 0; r < R; ++r) {
-            a.in[r] = static_cast<const uint8_t*>(out[r0 + r].base);
-            a.in_stride[r] = out[r0 + r].obj_stride;
-            a.out[r] = static_cast<uint8_t*>(views[k + r0 + r].base);
-            a.out_stride[r] = views[k + r0 + r].obj_stride;
-        }
-        a.shard_len = shard_len;
+        // input r: the recomputed row r0 + r, output r: the stored one; no tables
+        PassArgs a = make_pass(out.data(), views + k, nullptr, 0, r0, R, r0, R, shard_len);
         a.n_obj = n_obj;
-        const uint64_t want = (shard_len * n_obj + kBlockThreads - 1) / kBlockThreads;
-        const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, 16384));
-        e = launch_compare(R, a, flags, grid, stream);
-        if (e != hipSuccess) rc = hip_fail(e, "launch compare_views");
+        const int grid = grid_blocks(shard_len * n_obj, kBlockThreads, 16384);
+        rc = launched(launch_compare(R, a, flags, grid, stream), "launch compare_views");
     }
     hipError_t e2 = hipFreeAsync(scratch, stream);
     if (rc) return rc;
     if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync verify scratch");
     return HBEC_OK;
 }
+
+}  // namespace hbec
+
+extern "C" {
 
 int hbec_verify_batch(hbec_codec* c, const hbec_view* views, uint64_t n_objects, uint64_t shard_len,
                       uint32_t* d_flags, void* hip_stream) {
@@ -1746,8 +1662,10 @@ int hbec_coalesce_stats(uint64_t* groups, uint64_t* calls) {
 }
 
 int hbec_set_odd_chunk_tiles(uint64_t tiles) {
-    g_odd_chunk_override.store(tiles, std::memory_order_relaxed);
-    return HBEC_OK;
+    return hbec::guarded("hbec_set_odd_chunk_tiles", [&]() -> int {
+        g_odd_chunk_override.store(tiles, std::memory_order_relaxed);
+        return HBEC_OK;
+    });
 }
 
 int hbec_set_force_stream(int on) {
@@ -1772,7 +1690,7 @@ int hbec_kernel_info(int k, int r, uint64_t shard_len, int* tile_bytes, int* kin
             int dev = 0, cus = 0;
             int rc = current_device(&dev);
             if (rc) return rc;
-            rc = device_blocks(dev, k, r, pipe, packed ? 0 : fs, &cus, blocks_per_cu);
+            rc = device_blocks(dev, packed ? OccKind::Packed : vec_kind(pipe, fs), k, r, &cus, blocks_per_cu);
             if (rc) return rc;
             if (rec) *blocks_per_cu = odd_blocks_per_cu(0, k, r, false, true);
             if (g_blocks_per_cu_override > 0) *blocks_per_cu = g_blocks_per_cu_override;

@@ -125,12 +125,8 @@ size_t tune_size(const char* name, size_t dflt) {
 
 int ring_init(Ring& r, int dev) {
     r.dev = dev;
-    {
-        hipDeviceProp_t prop;
-        hipError_t pe = hipGetDeviceProperties(&prop, dev);
-        if (pe != hipSuccess) return hip_fail(pe, "hipGetDeviceProperties");
-        r.cus = prop.multiProcessorCount;
-    }
+    int rc = hbec::device_cus(dev, &r.cus);
+    if (rc) return rc;
     const size_t slot = env_size("HBEC_HOST_SLOT_MB", 64) << 20;  // IN bytes per slot
     r.in_cap = slot;
     r.out_cap = slot;  // outputs per piece <= inputs (R <= K) except tiny K: sized below per call

@@ -39,6 +39,10 @@ void set_thread_grid_cap(int blocks);
 int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, const hbec_view* out,
                 uint64_t n_obj, uint64_t shard_len, hipStream_t stream);
 
+// Compute units of device `dev`, from the per-device cache (hbec.cpp): the
+// one place the library asks the runtime for it.
+int device_cus(int dev, int* cus);
+
 // Stream-ordered device scratch from the library's private memory pool
 // (release threshold: never), so per-call scratch costs no real allocation.
 int scratch_alloc(size_t bytes, hipStream_t stream, void** out);

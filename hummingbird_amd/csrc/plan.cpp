@@ -277,13 +277,44 @@ int upload_verify(hbec_plan* p, hbec_codec* codec, hbec::VerifyRecs& vr) {
 
 std::atomic<uint64_t> g_vplan_launches{0}, g_vplan_per_stripe{0};
 
-int device_cus(int* cus) {
+// CU count of the current device
+int current_cus(int* cus) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-    e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute");
-    return HBEC_OK;
+    return hbec::device_cus(dev, cus);
+}
+
+// One pass of an unaligned plan: inputs [c0, c0 + K) and outputs [r0, r0 + R)
+// of the index lists with their coefficient tables; sel_k > 0: object records
+// (indices >= sel_k are parity, base b).
+hbec::UPlanArgs uplan_pass(const hbec::URec* recs, uint64_t n_recs, const std::vector<int>& in_idx,
+                           const std::vector<int>& out_idx, const std::vector<uint8_t>& rows, int sel_k, int r0, int R,
+                           int c0, int K) {
+    hbec::UPlanArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.recs = recs;
+    a.n_recs = (uint32_t)n_recs;
+    a.accumulate = c0 > 0 ? 1u : 0u;
+    for (int j = 0; j < K; ++j) {
+        int i = in_idx[c0 + j];
+        if (sel_k > 0 && i >= sel_k) {
+            a.in_sel |= 1u << j;
+            i -= sel_k;
+        }
+        a.in_idx[j] = (uint32_t)i;
+    }
+    for (int r = 0; r < R; ++r) {
+        int i = out_idx[r0 + r];
+        if (sel_k > 0 && i >= sel_k) {
+            a.out_sel |= 1u << r;
+            i -= sel_k;
+        }
+        a.out_idx[r] = (uint32_t)i;
+        for (int j = 0; j < K; ++j)
+            hbec::perm_table(rows[(size_t)(r0 + r) * in_idx.size() + c0 + j], a.tab[r][j]);
+    }
+    return a;
 }
 
 }  // namespace
@@ -305,7 +336,7 @@ int hbec::verify_recs_run(hbec_codec* codec, const VRec* d_recs, uint64_t n_recs
                           int max_blocks) {
     if (n_recs == 0) return HBEC_OK;
     int cus = 0;
-    int rc = device_cus(&cus);
+    int rc = current_cus(&cus);
     if (rc) return rc;
     hipError_t e = hbec::launch_verify_recs(hbec_data_shards(codec), hbec_parity_shards(codec), d_recs, (uint32_t)n_recs,
                                             d_tiles, (uint32_t)n_tiles, d_tab, d_flags, cus, stream, max_blocks);
@@ -334,11 +365,10 @@ int hbec::launch_unaligned_passes(const URec* recs, uint64_t n_recs, const std::
     if ((n_recs == 0 && n_erecs == 0) || R_all == 0) return HBEC_OK;
     if (mirror && (!hbec::odd_enabled() || sel_k > 0 || round2))
         return fail(HBEC_ERR_INVALID_ARG, "mirrored unaligned plans need gf_odd and stripe records");
-    int dev = 0, cus = 0, per_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute");
+    int cus = 0, per_cu = 0;
+    int rc = current_cus(&cus);
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
     if (hbec::odd_enabled() && !round2) {
         // per-stripe records over the plan's tile lists (unmirrored plans)
         const bool use_orecs = orecs && orecs->n > 0 && !mirror;
@@ -348,11 +378,7 @@ int hbec::launch_unaligned_passes(const URec* recs, uint64_t n_recs, const std::
             const int R = std::min(hbec::kMaxR, R_all - r0);
             for (int c0 = 0; c0 < K_all; c0 += hbec::kOddMaxK) {
                 const int K = std::min(hbec::kOddMaxK, K_all - c0);
-                hbec::UPlanArgs a;
-                std::memset(&a, 0, sizeof(a));
-                a.recs = recs;
-                a.n_recs = (uint32_t)n_recs;
-                a.accumulate = c0 > 0 ? 1u : 0u;
+                hbec::UPlanArgs a = uplan_pass(recs, n_recs, in_idx, out_idx, rows, sel_k, r0, R, c0, K);
                 // mirror: each pass's inputs once (first output group), the
                 // outputs when one input pass makes them final
                 if (mirror) a.mirror = (r0 == 0 ? 1u : 0u) | (K_all <= hbec::kOddMaxK ? 2u : 0u);
@@ -360,24 +386,6 @@ int hbec::launch_unaligned_passes(const URec* recs, uint64_t n_recs, const std::
                 a.carry = (!mirror && K <= 4 &&
                            hbec::urec_tile_for(std::min(K_all, hbec::kOddMaxK), false) != hbec::urec_tile_for(K, true))
                               ? 1u : 0u;
-                for (int j = 0; j < K; ++j) {
-                    int i = in_idx[c0 + j];
-                    if (sel_k > 0 && i >= sel_k) {
-                        a.in_sel |= 1u << j;
-                        i -= sel_k;
-                    }
-                    a.in_idx[j] = (uint32_t)i;
-                }
-                for (int r = 0; r < R; ++r) {
-                    int i = out_idx[r0 + r];
-                    if (sel_k > 0 && i >= sel_k) {
-                        a.out_sel |= 1u << r;
-                        i -= sel_k;
-                    }
-                    a.out_idx[r] = (uint32_t)i;
-                    for (int j = 0; j < K; ++j)
-                        hbec::perm_table(rows[(size_t)(r0 + r) * K_all + c0 + j], a.tab[r][j]);
-                }
                 const uint64_t want = (n_recs + 3) / 4;  // 4 waves per block
                 uint64_t cap = (uint64_t)cus * (uint64_t)hbec::odd_blocks_per_cu(c0 > 0 ? 1 : 0, K, R, mirror);
                 if (max_blocks > 0) cap = std::min<uint64_t>(cap, (uint64_t)max_blocks);
@@ -385,7 +393,7 @@ int hbec::launch_unaligned_passes(const URec* recs, uint64_t n_recs, const std::
                 const int mode = c0 > 0 ? 1 : 0;
                 bool fused = false;
                 if (use_orecs) {
-                    int rc = odd_stripe_rec_pass(K, R, mode, a, *orecs, cus, max_blocks, stream, K == K_all, &fused);
+                    rc = odd_stripe_rec_pass(K, R, mode, a, *orecs, cus, max_blocks, stream, K == K_all, &fused);
                     if (rc) return rc;
                 } else if (n_recs > 0) {
                     e = hbec::launch_odd_plan(K, R, mode, a, grid, stream);
@@ -430,28 +438,7 @@ int hbec::launch_unaligned_passes(const URec* recs, uint64_t n_recs, const std::
         if (const long long v = hbec::tune_knob("HBEC_UNALIGNED_BPC", 0); v > 0) per_cu = std::min(per_cu, (int)v);
         for (int c0 = 0; c0 < K_all; c0 += hbec::kMaxK) {
             const int K = std::min(hbec::kMaxK, K_all - c0);
-            hbec::UPlanArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.recs = recs;
-            a.n_recs = (uint32_t)n_recs;
-            a.accumulate = c0 > 0 ? 1u : 0u;
-            for (int j = 0; j < K; ++j) {
-                int i = in_idx[c0 + j];
-                if (sel_k > 0 && i >= sel_k) {
-                    a.in_sel |= 1u << j;
-                    i -= sel_k;
-                }
-                a.in_idx[j] = (uint32_t)i;
-            }
-            for (int r = 0; r < R; ++r) {
-                int i = out_idx[r0 + r];
-                if (sel_k > 0 && i >= sel_k) {
-                    a.out_sel |= 1u << r;
-                    i -= sel_k;
-                }
-                a.out_idx[r] = (uint32_t)i;
-                for (int j = 0; j < K; ++j) hbec::perm_table(rows[(size_t)(r0 + r) * K_all + c0 + j], a.tab[r][j]);
-            }
+            const hbec::UPlanArgs a = uplan_pass(recs, n_recs, in_idx, out_idx, rows, sel_k, r0, R, c0, K);
             const uint64_t want = (n_recs + 3) / 4;  // 4 waves per block
             uint64_t cap = (uint64_t)cus * std::max(1, per_cu);
             if (max_blocks > 0) cap = std::min<uint64_t>(cap, (uint64_t)max_blocks);
@@ -467,16 +454,12 @@ int hbec::stripes_grid(int k, int r, uint64_t n_tiles, int* grid, int blocks_per
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-    static int cus[64] = {0};
     static int occ[64][9][4] = {};
-    std::lock_guard<std::mutex> g(g_occ_mu);
     if (dev < 0 || dev >= 64) return fail(HBEC_ERR_DEVICE, "device index out of range");
-    if (cus[dev] == 0) {
-        hipDeviceProp_t p;
-        e = hipGetDeviceProperties(&p, dev);
-        if (e != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
-        cus[dev] = p.multiProcessorCount;
-    }
+    int cus = 0;
+    int rc = hbec::device_cus(dev, &cus);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(g_occ_mu);
     if (occ[dev][k][r] == 0) {
         int b = 0;
         e = hbec::stripes_occupancy(k, r, &b);
@@ -493,7 +476,7 @@ int hbec::stripes_grid(int k, int r, uint64_t n_tiles, int* grid, int blocks_per
         if (hbec::stripes_occupancy(k, r, &fit) != hipSuccess) fit = 1;
         bpc = std::max(1, std::min(fit, blocks_per_cu));
     }
-    uint64_t cap = (uint64_t)cus[dev] * (uint64_t)bpc;
+    uint64_t cap = (uint64_t)cus * (uint64_t)bpc;
     if (max_blocks > 0) cap = std::min<uint64_t>(cap, (uint64_t)max_blocks);
     *grid = (int)std::max<uint64_t>(1, std::min(want, cap));
     return HBEC_OK;
@@ -834,7 +817,7 @@ int hbec_verify_plan(hbec_codec* codec, const hbec_plan* plan, uint32_t* d_flags
             for (int r = 0; r < m; ++r)
                 for (int j = 0; j < k; ++j) hbec::perm_table(mat[(size_t)(k + r) * k + j], a.tab[r][j]);
             int cus = 0;
-            int rc = device_cus(&cus);
+            int rc = current_cus(&cus);
             if (rc) return rc;
             hipError_t e = hbec::launch_verify_tiles(k, m, a, plan->d_tiles, d_flags, cus, stream);
             if (e != hipSuccess) return hip_fail(e, "launch gf_verify_tiles");
