@@ -91,6 +91,10 @@ _SIG = [
      [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_encode_plan", C.c_int, [_P, _P, _P]),
     ("hbec_reconstruct_plan", C.c_int, [_P, _P, _U8P, C.c_int, _P]),
+    ("hbec_reconstruct_plan_mixed", C.c_int, [_P, _P, _U8P, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, _P]),
+    ("hbec_mixed_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_mixed_plan_tile_bytes", C.c_int, []),
+    ("hbec_set_mixed_plan_chunk_tiles", C.c_int, [C.c_uint64]),
     ("hbec_verify_plan", C.c_int, [_P, _P, _P, _P]),
     ("hbec_verify_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_verify_plan_tile_bytes", C.c_int, [C.c_int]),

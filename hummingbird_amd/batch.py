@@ -178,6 +178,26 @@ class StripePlan:
         p = (C.c_uint8 * len(present))(*[1 if x else 0 for x in present])
         check(N.lib().hbec_reconstruct_plan(self.enc.handle, self._h, p, int(data_only), _stream_ptr(stream)))
 
+    def reconstruct_mixed(self, present, data_only=False, stream=None):
+        """reconstruct with an erasure pattern per stripe / object: ``present``
+        is an [n, k+m] array, row i the mask of entry i of the array the plan
+        was built from (zero-length entries included; non-zero = shard read).
+        Equal rows share one pattern (hbec_reconstruct_plan_mixed)."""
+        import numpy as np
+
+        p = np.asarray(present) != 0
+        if p.ndim != 2 or p.shape[0] != self._n or p.shape[1] != self.enc.DataShards + self.enc.ParityShards:
+            raise ValueError("present must be [n_stripes, k+m]")
+        if self._n == 0:
+            patterns, pattern_of = p.astype(np.uint8), np.zeros(0, np.uint32)
+        else:
+            patterns, pattern_of = np.unique(p.astype(np.uint8), axis=0, return_inverse=True)
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        pattern_of = np.ascontiguousarray(pattern_of.reshape(-1), dtype=np.uint32)
+        check(N.lib().hbec_reconstruct_plan_mixed(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), int(data_only), _stream_ptr(stream)))
+
     def verify(self, flags, stream=None):
         """flags[i] |= 1 (uint32 CUDA tensor of len(stripes), caller-zeroed) for
         every stripe / object i whose stored parity differs from the recomputed
@@ -203,6 +223,25 @@ def verify_plan_stats():
 def verify_plan_tile_bytes(k: int) -> int:
     """Shard bytes per wave tile of the any-alignment plan Verify kernel."""
     return int(N.lib().hbec_verify_plan_tile_bytes(int(k)))
+
+
+def mixed_plan_stats():
+    """Since load, for StripePlan.reconstruct_mixed: launches of the mixed plan
+    kernel (`kernel_launches`) and single-pattern applies made one stripe at a
+    time for the shapes that kernel does not take (`per_stripe_calls`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_mixed_plan_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "per_stripe_calls": b.value}
+
+
+def mixed_plan_tile_bytes() -> int:
+    """Shard bytes per wave tile of the mixed plan kernel."""
+    return int(N.lib().hbec_mixed_plan_tile_bytes())
+
+
+def set_mixed_plan_chunk_tiles(tiles: int) -> None:
+    """Test hook: mixed plan kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_mixed_plan_chunk_tiles(int(tiles)))
 
 
 KERNEL_KINDS = {0: "unrolled", 1: "pipelined", 2: "streaming", 3: "packed", 4: "records"}

@@ -20,8 +20,8 @@ LIB = PKG / "libhbec.so"
 ROOT = PKG.parent
 INCLUDE = ROOT / "include"
 
-SOURCES = ["odd_k912.hip", "odd_k58.hip", "odd_bp.hip", "kernels.hip", "odd.hip", "wide.hip", "stripes.hip", "mixed.hip", "verify.hip", "vplan.hip", "md5.hip", "shardhash.cpp", "hbec.cpp", "ecutils.cpp", "plan.cpp", "hostpath.cpp", "batcher.cpp", "coalesce.cpp"]
-HEADERS = ["kernels.h", "gf256.h", "internal.h", "gf_device.h", "pool.h", "odd_impl.h", "tuning.h", "xor_sched.h", "mixed.h", "vplan.h"]
+SOURCES = ["odd_k912.hip", "odd_k58.hip", "odd_bp.hip", "kernels.hip", "odd.hip", "wide.hip", "stripes.hip", "mixed.hip", "mixedplan.hip", "verify.hip", "vplan.hip", "md5.hip", "shardhash.cpp", "hbec.cpp", "ecutils.cpp", "plan.cpp", "hostpath.cpp", "batcher.cpp", "coalesce.cpp"]
+HEADERS = ["kernels.h", "gf256.h", "internal.h", "gf_device.h", "pool.h", "odd_impl.h", "tuning.h", "xor_sched.h", "mixed.h", "vplan.h", "mixedplan.h", "unaligned_tile.h"]
 ARCH = os.environ.get("HBEC_OFFLOAD_ARCH", "gfx950")
 
 
@@ -104,6 +104,7 @@ ASAN_DIR = PKG / "build_asan"
 ASAN_LIB = ASAN_DIR / "libhbec_asan.so"
 ASAN_EXE = ASAN_DIR / "host_asan"
 ASAN_VERIFY_EXE = ASAN_DIR / "verify_plan_asan"
+ASAN_MIXED_PLAN_EXE = ASAN_DIR / "mixed_plan_asan"
 
 
 def build_asan(force: bool = False, verbose: bool = False) -> Path:
@@ -134,6 +135,17 @@ def build_asan(force: bool = False, verbose: bool = False) -> Path:
                "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__",
                "-I/opt/rocm/include", f"-I{INCLUDE}", str(vsrc), f"-L{ASAN_DIR}", "-lhbec_asan",
                f"-Wl,-rpath,{ASAN_DIR}", f"-Wl,-rpath,{rocm_lib}", "-lpthread", "-o", str(ASAN_VERIFY_EXE)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"clang failed:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
+    # the mixed plan reconstruct's host side, likewise over mixedplan.h
+    msrc = ROOT / "tests" / "native" / "mixed_plan_asan.cpp"
+    if force or _stale(ASAN_MIXED_PLAN_EXE, [msrc, lib, INCLUDE / "hbec.h", CSRC / "mixedplan.h", CSRC / "vplan.h",
+                                             CSRC / "kernels.h", CSRC / "gf256.h"]):
+        cmd = [clang + "++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+               "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__",
+               "-I/opt/rocm/include", f"-I{INCLUDE}", str(msrc), f"-L{ASAN_DIR}", "-lhbec_asan",
+               f"-Wl,-rpath,{ASAN_DIR}", f"-Wl,-rpath,{rocm_lib}", "-lpthread", "-o", str(ASAN_MIXED_PLAN_EXE)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"clang failed:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")

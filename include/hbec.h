@@ -288,6 +288,32 @@ int hbec_encode_plan(hbec_codec* codec, const hbec_plan* plan, void* hip_stream)
 /* Reconstruct every stripe with one erasure pattern (as hbec_reconstruct_batch). */
 int hbec_reconstruct_plan(hbec_codec* codec, const hbec_plan* plan, const uint8_t* present, int data_only,
                           void* hip_stream);
+/* hbec_reconstruct_plan with a pattern per stripe / object: a repair sweep over
+ * objects of any sizes that lost different shards.  patterns: n_patterns rows of
+ * k+m bytes (host), as in hbec_reconstruct_batch_mixed.  pattern_of (host): one
+ * index into patterns per entry of the array the plan was built from, zero-length
+ * entries included (the indexing of hbec_verify_plan's flags).  Entry i is rebuilt
+ * exactly as hbec_reconstruct_plan would rebuild it alone with
+ * patterns[pattern_of[i]]: survivors = its first k present shards, every missing
+ * shard written (missing data shards only with data_only), no other byte of it and
+ * no byte outside it written.  Both arrays are copied before the call returns; the
+ * work is queued on hip_stream and not waited for.  k <= 12 with m <= 4, at any
+ * alignment and shard length, is coded by one launch (per 2^31 - 1 tiles)
+ * whatever the number of stripes, patterns or rebuilt shards; other shapes, and shards of 2^31 - 64 KiB bytes or more, by one
+ * single-pattern apply per stripe.  Errors are found before anything is queued: a
+ * null argument, a plan built for another (k, m), n_patterns == 0 for a plan with
+ * entries or > 65536, an index >= n_patterns (zero-length entries too):
+ * HBEC_ERR_INVALID_ARG; a listed pattern with fewer than k present, used or not:
+ * HBEC_ERR_TOO_FEW_SHARDS.  A call with nothing to rebuild launches nothing.  The
+ * plan's device records for this call are built by the first such call. */
+int hbec_reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns,
+                                uint32_t n_patterns, const uint32_t* pattern_of, int data_only, void* hip_stream);
+/* launches since load of the mixed plan kernel, and per-stripe applies of the other route */
+int hbec_mixed_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
+/* shard bytes per wave tile of the mixed plan kernel */
+int hbec_mixed_plan_tile_bytes(void);
+/* test hook, as hbec_set_mixed_chunk_tiles: tiles per launch of the mixed plan kernel (0 = default) */
+int hbec_set_mixed_plan_chunk_tiles(uint64_t tiles);
 /* Encoder.Verify of every stripe / object of the plan: d_flags[i] |= 1 when stripe i (its
  * position in the array the plan was built from; n entries, device memory, caller-zeroed)
  * has a stored parity shard that differs from the recomputed one.  Zero-length stripes are
