@@ -36,6 +36,10 @@ class Stripe(C.Structure):
     _fields_ = [("base", C.c_void_p), ("shard_len", C.c_uint64)]
 
 
+class VerifyRoutes(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("packed", "pipe", "records", "odd", "wide", "unaligned", "scratch")]
+
+
 class Object(C.Structure):
     _fields_ = [("data", C.c_void_p), ("parity", C.c_void_p), ("shard_len", C.c_uint64)]
 
@@ -121,6 +125,7 @@ _SIG = [
     ("hbec_kernel_info", C.c_int,
      [C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("hbec_odd_path_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_verify_route_stats", C.c_int, [C.POINTER(VerifyRoutes)]),
     ("hbec_odd_edge_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_odd_record_cache", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_ec_shard_length", C.c_int64, [C.c_int64, C.c_int64]),

@@ -220,6 +220,15 @@ def verify_plan_stats():
     return {"plan_launches": a.value, "per_stripe_calls": b.value}
 
 
+def verify_route_stats():
+    """verify_views calls since load by the branch that answered them
+    (hbec_verify_route_stats): packed, pipe, records (16-B-aligned shapes sent
+    to the record kernels; counted under odd too), odd, wide, unaligned, scratch."""
+    r = N.VerifyRoutes()
+    check(N.lib().hbec_verify_route_stats(C.byref(r)))
+    return {n: getattr(r, n) for n, _ in N.VerifyRoutes._fields_}
+
+
 def verify_plan_tile_bytes(k: int) -> int:
     """Shard bytes per wave tile of the any-alignment plan Verify kernel."""
     return int(N.lib().hbec_verify_plan_tile_bytes(int(k)))

@@ -1431,6 +1431,11 @@ static int apply_wide(int rows, int cols, const uint8_t* coeffs, const hbec_view
                          });
 }
 
+// verify_views calls by the branch taken (hbec_verify_route_stats)
+enum VerifyRoute { kVrPacked, kVrPipe, kVrRecords, kVrOdd, kVrWide, kVrUnaligned, kVrScratch, kVrCount };
+static std::atomic<uint64_t> g_verify_routes[kVrCount];
+static void count_route(VerifyRoute r) { g_verify_routes[r].fetch_add(1, std::memory_order_relaxed); }
+
 static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, uint64_t shard_len, uint32_t* flags,
                         hipStream_t stream) {
     const int k = c->k, m = c->m;
@@ -1443,6 +1448,7 @@ static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, u
     if (rc) return rc;
     if (vec && is_verify_packed_shape(k, m, shard_len)) {
         // short shards: wave tiles across objects (gf_verify_packed)
+        count_route(kVrPacked);
         const PassArgs a = make_pass(views, views + k, prow, k, 0, m, 0, k, shard_len);
         rc = device_blocks(dev, OccKind::VerifyPacked, k, m, &cus, &bpc);
         if (rc) return rc;
@@ -1466,6 +1472,7 @@ static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, u
                           shard_len >= HBEC_REC_ROUTE_MIN_S && pos32_shard(shard_len) &&
                           bitplane_rows(k, m, prow, k, 2, false);
     if (vec && verify_supported(k, m) && !v_to_rec) {
+        count_route(kVrPipe);
         const PassArgs a = make_pass(views, views + k, prow, k, 0, m, 0, k, shard_len);
         const uint64_t tile = (uint64_t)verify_tile_bytes(k);
         const uint64_t tpo = (shard_len + tile - 1) / tile;
@@ -1498,6 +1505,8 @@ static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, u
     }
     if (odd_enabled() && odd_verify && pos32_shard(shard_len)) {
         // any alignment: recompute and compare in one pass (gf_odd verify), <= 4 rows per launch
+        count_route(kVrOdd);
+        if (v_to_rec) count_route(kVrRecords);
         for (int r0 = 0; r0 < m; r0 += kMaxR) {
             const int R = std::min(kMaxR, m - r0);
             rc = odd_launches(make_pass(views, views + k, prow, k, r0, R, 0, k, shard_len), k, R, 2, false, n_obj,
@@ -1509,10 +1518,12 @@ static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, u
     if (k > 8 && k <= 256 && pos32_shard(shard_len)) {
         // k > 8 at any alignment (k > 16 included): one read-only pass per <= 8
         // rows (gf_verify_wide, wide.hip), coefficient tables in LDS
+        count_route(kVrWide);
         return verify_wide(views, k, m, prow, n_obj, shard_len, flags, stream);
     }
     if (k <= kMaxK) {
         // any alignment: recompute and compare in one pass (gf_verify_unaligned), <= 4 rows per launch
+        count_route(kVrUnaligned);
         const uint64_t tpo = unaligned_tiles_per_obj(shard_len);
         for (int r0 = 0; r0 < m; r0 += kMaxR) {
             const int R = std::min(kMaxR, m - r0);
@@ -1530,6 +1541,7 @@ static int verify_views(hbec_codec* c, const hbec_view* views, uint64_t n_obj, u
         return HBEC_OK;
     }
     // generic: recompute parity into scratch, then compare bytewise
+    count_route(kVrScratch);
     uint8_t* scratch = nullptr;
     const size_t bytes = (size_t)n_obj * m * shard_len;
     hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&scratch), bytes, stream);
@@ -1560,6 +1572,16 @@ int hbec_verify_batch(hbec_codec* c, const hbec_view* views, uint64_t n_objects,
     return hbec::guarded("hbec_verify_batch", [&]() -> int {
         if (!c || !views || (!d_flags && n_objects)) return fail(HBEC_ERR_INVALID_ARG, "null argument");
         return verify_views(c, views, n_objects, shard_len, d_flags, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_verify_route_stats(hbec_verify_routes* out) {
+    return hbec::guarded("hbec_verify_route_stats", [&]() -> int {
+        if (!out) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        auto n = [](hbec::VerifyRoute r) { return hbec::g_verify_routes[r].load(std::memory_order_relaxed); };
+        *out = {n(hbec::kVrPacked), n(hbec::kVrPipe),      n(hbec::kVrRecords), n(hbec::kVrOdd),
+                n(hbec::kVrWide),   n(hbec::kVrUnaligned), n(hbec::kVrScratch)};
+        return HBEC_OK;
     });
 }
 

@@ -424,6 +424,17 @@ int hbec_kernel_info(int k, int r, uint64_t shard_len, int* tile_bytes, int* kin
  * strided = the table-multiply gf_odd / gf_odd_plan kernels.  Any pointer
  * may be NULL. */
 int hbec_odd_path_stats(uint64_t* bitplane, uint64_t* records, uint64_t* strided);
+/* hbec_verify_batch calls since load (and the per-stripe ones of hbec_verify /
+ * hbec_verify_plan's other route) by the branch that answered them: packed =
+ * gf_verify_packed, pipe = gf_verify_pipe, records = 16-B-aligned shapes sent to
+ * the record kernels, odd = the gf_odd Verify families at any alignment (told
+ * apart by hbec_odd_path_stats), wide = gf_verify_wide, unaligned =
+ * gf_verify_unaligned, scratch = recompute into scratch and compare.  records
+ * calls count under odd too.  Calls with nothing to verify count nowhere. */
+typedef struct hbec_verify_routes {
+    uint64_t packed, pipe, records, odd, wide, unaligned, scratch;
+} hbec_verify_routes;
+int hbec_verify_route_stats(hbec_verify_routes* out);
 
 /* Odd-shard guard bands (the <= 64 head and tail bytes of each shard the main
  * kernels' 16-B frame does not store): launches since load of the separate

@@ -1,7 +1,7 @@
 // Host-only checks of the plan Verify under AddressSanitizer + UBSan (no GPU
 // work): the routing of stripes to Verify records and their flag indices
 // (vplan.h vp_add), and every argument check of hbec_verify_plan /
-// hbec_verify_host / hbec_verify_plan_stats, which answer before a device is
+// hbec_verify_host / hbec_verify_plan_stats / hbec_verify_route_stats, which answer before a device is
 // touched.  Linked against the sanitized libhbec (build.py build_asan).
 #include <cstdio>
 #include <cstdlib>
@@ -96,6 +96,10 @@ static int arguments() {
     CHECK(hbec_verify_plan_stats(nullptr, &b) == HBEC_ERR_INVALID_ARG);
     CHECK(hbec_verify_plan_stats(&a, nullptr) == HBEC_ERR_INVALID_ARG);
     CHECK(hbec_verify_plan_stats(&a, &b) == HBEC_OK && a == 0 && b == 0);
+    hbec_verify_routes vr;
+    CHECK(hbec_verify_route_stats(nullptr) == HBEC_ERR_INVALID_ARG);
+    CHECK(hbec_verify_route_stats(&vr) == HBEC_OK);
+    CHECK(vr.packed + vr.pipe + vr.records + vr.odd + vr.wide + vr.unaligned + vr.scratch == 0);  // nothing reached a route
     CHECK(hbec_verify_plan_tile_bytes(8) == (int)hbec::kVpTile);
     for (hbec_plan* p : {ps, po, p0, pm}) hbec_plan_free(p);
     hbec_free(c42);

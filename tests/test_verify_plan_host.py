@@ -108,6 +108,11 @@ def test_stats_and_tile_bytes_answer():
     a = C.c_uint64()
     assert L.hbec_verify_plan_stats(None, C.byref(a)) == N.ERR_INVALID_ARG
     assert L.hbec_verify_plan_stats(C.byref(a), None) == N.ERR_INVALID_ARG
+    assert L.hbec_verify_route_stats(None) == N.ERR_INVALID_ARG
+    assert "null" in N.last_error()
+    r0 = B.verify_route_stats()
+    assert list(r0) == ["packed", "pipe", "records", "odd", "wide", "unaligned", "scratch"]
+    assert B.verify_route_stats() == r0  # nothing was verified here
     s0 = B.verify_plan_stats()
     assert set(s0) == {"plan_launches", "per_stripe_calls"}
     assert B.verify_plan_stats() == s0  # nothing was launched here
