@@ -210,6 +210,33 @@ class StripePlan:
             raise ValueError("flags must be a contiguous CUDA tensor with one entry per stripe")
         check(N.lib().hbec_verify_plan(self.enc.handle, self._h, C.c_void_p(flags.data_ptr()), _stream_ptr(stream)))
 
+    def verify_mixed(self, present, flags, stream=None):
+        """verify for a plan whose entries are missing different shards:
+        ``present`` is an [n, k+m] array as in reconstruct_mixed.  Per entry the
+        present shards beyond its first k present are checked against what those
+        k imply: flags[i] |= 1 on a mismatch, |= 2 when exactly k are present and
+        nothing could be checked (hbec_verify_plan_mixed).  flags as in verify;
+        read-only, queued on the stream."""
+        import numpy as np
+        import torch
+
+        if flags.dtype != torch.uint32 and flags.dtype != torch.int32:
+            raise ValueError("flags must be a 32-bit integer tensor")
+        if not flags.is_cuda or not flags.is_contiguous() or flags.numel() < self._n:
+            raise ValueError("flags must be a contiguous CUDA tensor with one entry per stripe")
+        p = np.asarray(present) != 0
+        if p.ndim != 2 or p.shape[0] != self._n or p.shape[1] != self.enc.DataShards + self.enc.ParityShards:
+            raise ValueError("present must be [n_stripes, k+m]")
+        if self._n == 0:
+            patterns, pattern_of = p.astype(np.uint8), np.zeros(0, np.uint32)
+        else:
+            patterns, pattern_of = np.unique(p.astype(np.uint8), axis=0, return_inverse=True)
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        pattern_of = np.ascontiguousarray(pattern_of.reshape(-1), dtype=np.uint32)
+        check(N.lib().hbec_verify_plan_mixed(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(flags.data_ptr()), _stream_ptr(stream)))
+
 
 def verify_plan_stats():
     """Since load: launches of the plan Verify kernels (`plan_launches`) and
@@ -251,6 +278,25 @@ def mixed_plan_tile_bytes() -> int:
 def set_mixed_plan_chunk_tiles(tiles: int) -> None:
     """Test hook: mixed plan kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_mixed_plan_chunk_tiles(int(tiles)))
+
+
+def verify_mixed_plan_stats():
+    """Since load, for StripePlan.verify_mixed: launches of the mixed plan Verify
+    kernel (`kernel_launches`) and stripes verified one at a time for the shapes
+    that kernel does not take (`per_stripe_calls`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_verify_mixed_plan_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "per_stripe_calls": b.value}
+
+
+def verify_mixed_plan_tile_bytes() -> int:
+    """Shard bytes per wave tile of the mixed plan Verify kernel."""
+    return int(N.lib().hbec_verify_mixed_plan_tile_bytes())
+
+
+def set_verify_mixed_plan_chunk_tiles(tiles: int) -> None:
+    """Test hook: mixed plan Verify kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_verify_mixed_plan_chunk_tiles(int(tiles)))
 
 
 KERNEL_KINDS = {0: "unrolled", 1: "pipelined", 2: "streaming", 3: "packed", 4: "records"}

@@ -32,6 +32,7 @@
 #include "internal.h"
 #include "kernels.h"
 #include "mixed.h"
+#include "vmixed.h"
 
 namespace hbec {
 
@@ -1260,6 +1261,32 @@ int hbec_decode_rows(hbec_codec* c, const uint8_t* present, int data_only, int* 
         std::copy(outs.begin(), outs.end(), outputs);
         *n_outputs = (int)outs.size();
         std::copy(r.begin(), r.end(), rows);
+        return HBEC_OK;
+    });
+}
+
+int hbec_check_rows(hbec_codec* c, const uint8_t* present, int* survivors, int* checked, int* n_checked,
+                    uint8_t* rows) {
+    return hbec::guarded("hbec_check_rows", [&]() -> int {
+        if (!c || !present || !survivors || !checked || !n_checked || !rows)
+            return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        const int k = c->k, n = c->k + c->m;
+        // the rows Reconstruct would use for every shard but the survivors
+        std::vector<int> surv(k), chk(n), outs;
+        int nc = 0;
+        if (!hbec::vm_select(k, n, present, surv.data(), chk.data(), &nc))
+            return fail(HBEC_ERR_TOO_FEW_SHARDS, "too few shards given");
+        std::vector<uint8_t> only(n, 0), r;
+        for (int i : surv) only[i] = 1;
+        int rc = decode_rows(c, only, false, surv, outs, r);
+        if (rc) return rc;
+        std::copy(surv.begin(), surv.end(), survivors);
+        for (int q = 0, o = 0; q < nc; ++q, ++o) {  // both ascending
+            while (outs[o] != chk[q]) ++o;
+            checked[q] = chk[q];
+            std::copy(r.begin() + (size_t)o * k, r.begin() + (size_t)(o + 1) * k, rows + (size_t)q * k);
+        }
+        *n_checked = nc;
         return HBEC_OK;
     });
 }

@@ -9,7 +9,9 @@
 // runs over the same tile records plus per-stripe records of its own
 // (vplan.h, vplan.hip).  Reconstruct with an erasure pattern per stripe
 // (hbec_reconstruct_plan_mixed) runs over per-source-entry records and a tile
-// list of its own, built on first use (mixedplan.h, mixedplan.hip).
+// list of its own, built on first use (mixedplan.h, mixedplan.hip); Verify with
+// a present mask per stripe (hbec_verify_plan_mixed) reads the same records and
+// list (vmixed.h, vmixed.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +27,7 @@
 #include "internal.h"
 #include "kernels.h"
 #include "mixedplan.h"
+#include "vmixed.h"
 #include "vplan.h"
 
 using hbec::fail;
@@ -68,7 +71,8 @@ struct hbec_plan {
     uint32_t* d_vtab = nullptr;  // [k][vp_tab_stride(m)] parity coefficient tables
     uint64_t n_vrecs = 0, n_vtiles = 0;
     std::vector<hbec::VOther> vother;
-    // Reconstruct with a pattern per stripe (hbec_reconstruct_plan_mixed): where
+    // Reconstruct and Verify with a pattern per stripe (hbec_reconstruct_plan_mixed,
+    // hbec_verify_plan_mixed): where
     // every source entry lives, by its position in the caller's array; the
     // device records and the static {entry, tile} list are built by the first
     // such call (mp_mu), so a plan that never makes one pays for neither.
@@ -612,16 +616,18 @@ struct PlanPattern {
     uint32_t rec = 0;           // its pattern record (kernel route)
 };
 
-int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                           const uint32_t* pattern_of, bool data_only, hipStream_t stream) {
+// The argument checks of a call with a pattern per source entry
+// (hbec_reconstruct_plan_mixed, hbec_verify_plan_mixed), all made before anything
+// is queued; counts the non-empty entries of every pattern.
+int check_plan_patterns(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                        const uint32_t* pattern_of, std::vector<PlanPattern>& pats) {
     if (!codec || !plan || !patterns || !pattern_of) return fail(HBEC_ERR_INVALID_ARG, "null argument");
     const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
     if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
     if (n_patterns > 65536) return fail(HBEC_ERR_INVALID_ARG, "more than 65536 patterns");
     const uint64_t n_src = plan->n_src;
     if (n_src && !n_patterns) return fail(HBEC_ERR_INVALID_ARG, "stripes but no patterns");
-    std::vector<PlanPattern> pats(n_patterns);
-    std::vector<uint8_t> mask((size_t)n);
+    pats.assign(n_patterns, PlanPattern());
     for (uint32_t p = 0; p < n_patterns; ++p) {
         int n_present = 0;
         for (int i = 0; i < n; ++i) n_present += patterns[(size_t)p * n + i] ? 1 : 0;
@@ -633,6 +639,60 @@ int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8
             return fail(HBEC_ERR_INVALID_ARG, "pattern index out of range (stripe " + std::to_string(i) + ")");
         if (plan->src[i].shard_len) ++pats[pattern_of[i]].uses;
     }
+    return HBEC_OK;
+}
+
+// After a call's launches: the next call on another stream waits for them.
+int stage_end(const hbec_plan* plan, hipStream_t stream) {
+    plan->mp_stream = stream;
+    const hipError_t e = hipEventRecord(plan->mp_ev, stream);
+    return e == hipSuccess ? HBEC_OK : hip_fail(e, "hipEventRecord (plan mixed staging)");
+}
+
+// A call's staging words (pattern records, then one word per source entry) go
+// to a buffer the plan owns, not to stream-ordered scratch: with a scratch
+// allocation and a copy from pageable memory per call, a call returned only
+// when the one before it had run (4096 stripes 4+2: 0.70 of a call's 0.74 ms
+// on the host, against 0.016 ms for hbec_reconstruct_plan), so back-to-back
+// calls never overlapped.  Up to kMPlanPutBytes the words travel in kernel
+// arguments (launch_put_words).  Calls on one plan, reconstruct and verify
+// alike, take turns under mp_mu from stage_begin to stage_end; a call on
+// another stream than the last waits for that call's event, so the words of one
+// call are never overwritten while its launches may still read them.
+int stage_begin(const hbec_plan* plan, const std::vector<uint32_t>& stage, hipStream_t stream) {
+    hipError_t e = hipSuccess;
+    if (stage.size() > plan->mstage_words) {
+        if (plan->d_mstage) (void)hipFree(plan->d_mstage);  // waits for the work that reads it
+        plan->d_mstage = nullptr;
+        plan->mstage_words = 0;
+        const size_t cap = std::max<size_t>(2 * stage.size(), 4096);
+        e = hipMalloc(reinterpret_cast<void**>(&plan->d_mstage), cap * 4);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc plan mixed staging");
+        plan->mstage_words = cap;
+    }
+    if (!plan->mp_ev) {
+        e = hipEventCreateWithFlags(&plan->mp_ev, hipEventDisableTiming);
+        if (e != hipSuccess) return hip_fail(e, "hipEventCreate (plan mixed staging)");
+    } else if (plan->mp_stream != stream) {
+        e = hipStreamWaitEvent(stream, plan->mp_ev, 0);
+        if (e != hipSuccess) return hip_fail(e, "hipStreamWaitEvent (plan mixed staging)");
+    }
+    e = stage.size() * 4 <= kMPlanPutBytes
+            ? hbec::launch_put_words(plan->d_mstage, stage.data(), stage.size() * 4, stream)
+            : hipMemcpyAsync(plan->d_mstage, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) return HBEC_OK;
+    (void)stage_end(plan, stream);
+    return hip_fail(e, "plan mixed staging");
+}
+
+int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                           const uint32_t* pattern_of, bool data_only, hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
+    const uint64_t n_src = plan->n_src;
+    std::vector<uint8_t> mask((size_t)n);
     bool work = false;
     for (uint32_t p = 0; p < n_patterns; ++p) {
         PlanPattern& pp = pats[p];
@@ -656,7 +716,7 @@ int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8
         work = work || n_out > 0;
     }
     if (!work) return HBEC_OK;
-    int rc = mixed_plan_device(plan);
+    rc = mixed_plan_device(plan);
     if (rc) return rc;
 
     if (plan->n_mtiles > 0) {
@@ -681,38 +741,12 @@ int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8
         int cus = 0;
         rc = current_cus(&cus);
         if (rc) return rc;
-        // The words go to a buffer the plan owns, not to stream-ordered scratch:
-        // with a scratch allocation and a copy from pageable memory per call,
-        // a call returned only when the one before it had run (4096 stripes
-        // 4+2: 0.70 of a call's 0.74 ms on the host, against 0.016 ms for
-        // hbec_reconstruct_plan), so back-to-back calls never overlapped.  Up to
-        // kMPlanPutBytes the words travel in kernel arguments
-        // (launch_put_words).  Calls on one plan take turns here; a call on
-        // another stream than the last waits for that call's event.
         std::lock_guard<std::mutex> lk(plan->mp_mu);
-        hipError_t e = hipSuccess;
-        if (stage.size() > plan->mstage_words) {
-            if (plan->d_mstage) (void)hipFree(plan->d_mstage);  // waits for the work that reads it
-            plan->d_mstage = nullptr;
-            plan->mstage_words = 0;
-            const size_t cap = std::max<size_t>(2 * stage.size(), 4096);
-            e = hipMalloc(reinterpret_cast<void**>(&plan->d_mstage), cap * 4);
-            if (e != hipSuccess) return hip_fail(e, "hipMalloc plan mixed staging");
-            plan->mstage_words = cap;
-        }
-        if (!plan->mp_ev) {
-            e = hipEventCreateWithFlags(&plan->mp_ev, hipEventDisableTiming);
-            if (e != hipSuccess) return hip_fail(e, "hipEventCreate (plan mixed staging)");
-        } else if (plan->mp_stream != stream) {
-            e = hipStreamWaitEvent(stream, plan->mp_ev, 0);
-            if (e != hipSuccess) return hip_fail(e, "hipStreamWaitEvent (plan mixed staging)");
-        }
-        uint32_t* d = plan->d_mstage;
-        const uint32_t* d_pats = d;
+        rc = stage_begin(plan, stage, stream);
+        if (rc) return rc;
+        const uint32_t* d_pats = plan->d_mstage;
         const uint32_t* d_words = d_pats + rec_words;
-        e = stage.size() * 4 <= kMPlanPutBytes
-                           ? hbec::launch_put_words(d, stage.data(), stage.size() * 4, stream)
-                           : hipMemcpyAsync(d, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, stream);
+        hipError_t e = hipSuccess;
         const uint64_t hook = g_mplan_chunk_override.load(std::memory_order_relaxed);
         const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
         // one launch per chunk of the list, of the instance for the largest
@@ -725,10 +759,9 @@ int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8
             g_mplan_launches.fetch_add(1, std::memory_order_relaxed);
             e = hbec::launch_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats, cus, stream);
         }
-        plan->mp_stream = stream;
-        const hipError_t e2 = hipEventRecord(plan->mp_ev, stream);
+        rc = stage_end(plan, stream);
         if (e != hipSuccess) return hip_fail(e, "launch gf_mixed_plan");
-        if (e2 != hipSuccess) return hip_fail(e2, "hipEventRecord (plan mixed staging)");
+        if (rc) return rc;
     }
     // the other route: one single-pattern apply per stripe (any k, m, S)
     std::vector<hbec_view> vin((size_t)k), vout;
@@ -746,6 +779,121 @@ int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8
         g_mplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
         rc = hbec::apply_views((int)pp.outs.size(), k, pp.rows.data(), vin.data(), vout.data(), 1, s.shard_len, stream);
         if (rc) return rc;
+    }
+    return HBEC_OK;
+}
+
+// ---- Verify with a present mask per stripe (hbec_verify_plan_mixed) ----
+
+std::atomic<uint64_t> g_vmplan_launches{0}, g_vmplan_per_stripe{0};
+// test hook (hbec_set_verify_mixed_plan_chunk_tiles): tiles per gf_verify_mixed_plan launch
+std::atomic<uint64_t> g_vmplan_chunk_override{0};
+
+int verify_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                      const uint32_t* pattern_of, uint32_t* d_flags, hipStream_t stream) {
+    std::vector<PlanPattern> pats;  // outs: the checked shards
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    if (!d_flags && plan->n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
+    const uint64_t n_src = plan->n_src;
+    std::vector<uint8_t> mask((size_t)n);
+    bool used = false;
+    for (uint32_t p = 0; p < n_patterns; ++p) {
+        PlanPattern& pp = pats[p];
+        if (!pp.uses) continue;
+        used = true;
+        for (int i = 0; i < n; ++i) mask[i] = patterns[(size_t)p * n + i] ? 1 : 0;
+        pp.surv.resize(k);
+        pp.outs.resize(std::max(1, m));
+        pp.rows.resize((size_t)std::max(1, m) * k);
+        int n_checked = 0;
+        rc = hbec_check_rows(codec, mask.data(), pp.surv.data(), pp.outs.data(), &n_checked, pp.rows.data());
+        if (rc) return rc;
+        pp.outs.resize(n_checked);
+        pp.rows.resize((size_t)n_checked * k);
+    }
+    if (!used) return HBEC_OK;  // zero-length entries only
+    rc = mixed_plan_device(plan);
+    if (rc) return rc;
+    int cus = 0;
+    rc = current_cus(&cus);
+    if (rc) return rc;
+
+    if (plan->n_mtiles > 0) {
+        // per call, as reconstruct_plan_mixed: the records of the masks with
+        // something to check and one word per source entry, in one buffer
+        std::vector<uint32_t> stage;
+        for (PlanPattern& pp : pats) {
+            if (!pp.uses || pp.outs.empty()) continue;
+            pp.rec = hbec::vm_pattern(stage, k, pp.surv.data(), pp.outs.data(), (int)pp.outs.size(), pp.rows.data());
+        }
+        const size_t rec_words = stage.size();
+        stage.resize(rec_words + (size_t)n_src);
+        uint32_t* words = stage.data() + rec_words;
+        int rmax = 1;  // exactly-k entries alone: any instance sets their bit
+        for (uint64_t i = 0; i < n_src; ++i) {
+            const PlanPattern& pp = pats[pattern_of[i]];
+            const bool kernel = hbec::vm_route(k, m, plan->src[i].shard_len) == hbec::kVmKernel;
+            words[i] = kernel ? hbec::vm_word((int)pp.outs.size(), pp.rec) : 0u;
+            if (kernel) rmax = std::max(rmax, (int)pp.outs.size());
+        }
+        std::lock_guard<std::mutex> lk(plan->mp_mu);
+        rc = stage_begin(plan, stage, stream);
+        if (rc) return rc;
+        const uint32_t* d_pats = plan->d_mstage;
+        const uint32_t* d_words = d_pats + rec_words;
+        hipError_t e = hipSuccess;
+        const uint64_t hook = g_vmplan_chunk_override.load(std::memory_order_relaxed);
+        const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
+        // one launch per chunk of the list, of the instance for the largest count
+        // of checked shards in use
+        for (uint64_t t0 = 0; t0 < plan->n_mtiles && e == hipSuccess; t0 += chunk) {
+            const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
+            g_vmplan_launches.fetch_add(1, std::memory_order_relaxed);
+            e = hbec::launch_verify_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats,
+                                               d_flags, cus, stream);
+        }
+        rc = stage_end(plan, stream);
+        if (e != hipSuccess) return hip_fail(e, "launch gf_verify_mixed_plan");
+        if (rc) return rc;
+    }
+    // the other route, one stripe at a time (any k, m, S): all present, the
+    // per-stripe Verify; degraded, the checked shards rebuilt from the survivors
+    // into scratch and compared with the stored ones
+    std::vector<hbec_view> vin((size_t)k), vout;
+    for (uint32_t i : plan->mp_other) {
+        const PlanPattern& pp = pats[pattern_of[i]];
+        const hbec::MSrc& s = plan->src[i];
+        g_vmplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
+        if (pp.outs.empty()) {
+            const hipError_t e = hbec::launch_vm_or(d_flags + i, 2u, stream);
+            if (e != hipSuccess) return hip_fail(e, "launch gf_vm_or");
+            continue;
+        }
+        if ((int)pp.outs.size() == m) {
+            rc = hbec::verify_other_run(codec, hbec::VOther{s.a, s.b, s.shard_len, i}, d_flags, stream);
+            if (rc) return rc;
+            continue;
+        }
+        auto at = [&](int sh) {
+            return sh < k ? s.a + (uint64_t)sh * s.shard_len : s.b + (uint64_t)(sh - k) * s.shard_len;
+        };
+        void* scratch = nullptr;
+        rc = hbec::scratch_alloc(pp.outs.size() * (size_t)s.shard_len, stream, &scratch);
+        if (rc) return rc;
+        uint8_t* rebuilt = static_cast<uint8_t*>(scratch);
+        vout.resize(pp.outs.size());
+        for (int j = 0; j < k; ++j) vin[j] = hbec_view{reinterpret_cast<void*>(at(pp.surv[j])), 0};
+        for (size_t q = 0; q < pp.outs.size(); ++q) vout[q] = hbec_view{rebuilt + q * (size_t)s.shard_len, 0};
+        rc = hbec::apply_views((int)pp.outs.size(), k, pp.rows.data(), vin.data(), vout.data(), 1, s.shard_len, stream);
+        hipError_t e = hipSuccess;
+        for (size_t q = 0; q < pp.outs.size() && !rc && e == hipSuccess; ++q)
+            e = hbec::launch_vm_compare(rebuilt + q * (size_t)s.shard_len, reinterpret_cast<const void*>(at(pp.outs[q])),
+                                        s.shard_len, d_flags + i, cus, stream);
+        hbec::scratch_free(scratch, stream);
+        if (rc) return rc;
+        if (e != hipSuccess) return hip_fail(e, "launch gf_vm_compare");
     }
     return HBEC_OK;
 }
@@ -1026,6 +1174,32 @@ int hbec_mixed_plan_tile_bytes(void) { return (int)hbec::mixed_plan_tile_bytes()
 int hbec_set_mixed_plan_chunk_tiles(uint64_t tiles) {
     return hbec::guarded("hbec_set_mixed_plan_chunk_tiles", [&]() -> int {
         g_mplan_chunk_override.store(tiles, std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_verify_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                           const uint32_t* pattern_of, uint32_t* d_flags, void* hip_stream) {
+    return hbec::guarded("hbec_verify_plan_mixed", [&]() -> int {
+        return verify_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, d_flags,
+                                 static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_verify_mixed_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
+    return hbec::guarded("hbec_verify_mixed_plan_stats", [&]() -> int {
+        if (!kernel_launches || !per_stripe_calls) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *kernel_launches = g_vmplan_launches.load(std::memory_order_relaxed);
+        *per_stripe_calls = g_vmplan_per_stripe.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_verify_mixed_plan_tile_bytes(void) { return (int)hbec::verify_mixed_plan_tile_bytes(); }
+
+int hbec_set_verify_mixed_plan_chunk_tiles(uint64_t tiles) {
+    return hbec::guarded("hbec_set_verify_mixed_plan_chunk_tiles", [&]() -> int {
+        g_vmplan_chunk_override.store(tiles, std::memory_order_relaxed);
         return HBEC_OK;
     });
 }

@@ -255,6 +255,20 @@ class Encoder:
         r = np.frombuffer(bytes(rows), dtype=np.uint8)[: nout.value * self.DataShards]
         return list(surv), list(outs)[: nout.value], r.reshape(nout.value, self.DataShards)
 
+    def check_rows(self, present):
+        """(survivors, checked, rows) of the degraded Verify (hbec_check_rows):
+        the first k present shards, the other present shards, and per checked
+        shard the row that rebuilds it from the survivors."""
+        n, k, m = self.Shards, self.DataShards, self.ParityShards
+        p = (C.c_uint8 * n)(*[1 if x else 0 for x in present])
+        surv = (C.c_int * k)()
+        chk = (C.c_int * max(1, m))()
+        nchk = C.c_int()
+        rows = (C.c_uint8 * (max(1, m) * k))()
+        check(N.lib().hbec_check_rows(self._h, p, surv, chk, C.byref(nchk), rows))
+        r = np.frombuffer(bytes(rows), dtype=np.uint8)[: nchk.value * k]
+        return list(surv), list(chk)[: nchk.value], r.reshape(nchk.value, k)
+
 
 class Batcher:
     """hbec_batcher: concurrent callers each submit one host stripe (ecSplit

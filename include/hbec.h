@@ -326,6 +326,43 @@ int hbec_verify_plan(hbec_codec* codec, const hbec_plan* plan, uint32_t* d_flags
 int hbec_verify_plan_stats(uint64_t* plan_launches, uint64_t* per_stripe_calls);
 /* shard bytes per wave tile of the any-alignment plan Verify kernel (k data shards) */
 int hbec_verify_plan_tile_bytes(int k);
+/* Verify of a plan whose stripes / objects are missing different shards (a disk is down or
+ * being drained: auditor.go:100-156; the survivors ecReconstruct is about to rebuild from,
+ * ecutils.go:94-111).  patterns / n_patterns / pattern_of: host arrays exactly as in
+ * hbec_reconstruct_plan_mixed (indexed by the array the plan was built from, zero-length
+ * entries included; both copied before the call returns).  For entry i with mask
+ * patterns[pattern_of[i]]: survivors = its first k present shards, checked = its other
+ * present shards (hbec_check_rows); d_flags[i] |= 1 when some checked shard differs at
+ * some byte from what the survivors imply, |= 2 when exactly k shards are present and
+ * nothing could be checked.  With every shard present this is Encoder.Verify.  One flipped
+ * bit in any present shard, survivor or checked, sets bit 0; a missing shard is never
+ * compared.  d_flags: uint32, device, one entry per source entry as hbec_verify_plan's;
+ * zero-length entries are never touched and bits the caller had set stay.  Read-only apart
+ * from the flags; queued on hip_stream and not waited for.  k <= 12 with m <= 4, at any
+ * alignment and shard length, takes one launch (per 2^31 - 1 tiles) whatever the number of
+ * stripes, patterns or checked shards; other shapes, and shards of 2^31 - 64 KiB bytes or
+ * more, one call per stripe (all present: the per-stripe Verify; degraded: the checked
+ * shards rebuilt into scratch and compared).  Errors are found before anything is queued
+ * and before any flag is written, and are hbec_reconstruct_plan_mixed's: a null argument,
+ * a plan built for another (k, m), n_patterns == 0 for a plan with entries or > 65536, an
+ * index >= n_patterns (zero-length entries too): HBEC_ERR_INVALID_ARG; a listed pattern
+ * with fewer than k present, used or not: HBEC_ERR_TOO_FEW_SHARDS.  d_flags may be NULL
+ * only for a plan built from no entries. */
+int hbec_verify_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                           const uint32_t* pattern_of, uint32_t* d_flags, void* hip_stream);
+/* What hbec_verify_plan_mixed checks for one mask (auditor.go:100-156, ecutils.go:94-111;
+ * host only, no GPU): survivors[0..k) = the first k present shards, checked[0..*n_checked)
+ * = the other present shards (at most m), rows[*n_checked][k] = the decode row that rebuilds
+ * each checked shard from the survivors.  Fewer than k present: HBEC_ERR_TOO_FEW_SHARDS. */
+int hbec_check_rows(hbec_codec* codec, const uint8_t* present, int* survivors, int* checked, int* n_checked,
+                    uint8_t* rows);
+/* launches since load of the mixed plan Verify kernel, and per-stripe calls of the other route
+ * (auditor.go:100-156, ecutils.go:94-111) */
+int hbec_verify_mixed_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
+/* shard bytes per wave tile of the mixed plan Verify kernel */
+int hbec_verify_mixed_plan_tile_bytes(void);
+/* test hook, as hbec_set_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
+int hbec_set_verify_mixed_plan_chunk_tiles(uint64_t tiles);
 
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
