@@ -40,6 +40,10 @@ class VerifyRoutes(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("packed", "pipe", "records", "odd", "wide", "unaligned", "scratch")]
 
 
+class ApplyRoutes(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("packed", "vec", "odd", "unaligned", "wide")]
+
+
 class Object(C.Structure):
     _fields_ = [("data", C.c_void_p), ("parity", C.c_void_p), ("shard_len", C.c_uint64)]
 
@@ -132,6 +136,7 @@ _SIG = [
      [C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("hbec_odd_path_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_verify_route_stats", C.c_int, [C.POINTER(VerifyRoutes)]),
+    ("hbec_apply_route_stats", C.c_int, [C.POINTER(ApplyRoutes)]),
     ("hbec_odd_edge_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_odd_record_cache", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_ec_shard_length", C.c_int64, [C.c_int64, C.c_int64]),

@@ -256,6 +256,15 @@ def verify_route_stats():
     return {n: getattr(r, n) for n, _ in N.VerifyRoutes._fields_}
 
 
+def apply_route_stats():
+    """apply_views passes since load by the branch that coded them
+    (hbec_apply_route_stats): packed, vec, odd (the gf_odd families, 16-B-aligned
+    shapes sent to the record kernels included), unaligned, wide (one per call)."""
+    r = N.ApplyRoutes()
+    check(N.lib().hbec_apply_route_stats(C.byref(r)))
+    return {n: getattr(r, n) for n, _ in N.ApplyRoutes._fields_}
+
+
 def verify_plan_tile_bytes(k: int) -> int:
     """Shard bytes per wave tile of the any-alignment plan Verify kernel."""
     return int(N.lib().hbec_verify_plan_tile_bytes(int(k)))

@@ -461,6 +461,11 @@ static bool line_aligned(const void* p, uint64_t stride) {
 static int apply_wide(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, const hbec_view* out,
                       uint64_t n_obj, uint64_t shard_len, hipStream_t stream);
 
+// apply_views passes by the branch taken (hbec_apply_route_stats); a gf_wide call counts once
+enum ApplyRoute { kArPacked, kArVec, kArOdd, kArUnaligned, kArWide, kArCount };
+static std::atomic<uint64_t> g_apply_routes[kArCount];
+static void count_apply(ApplyRoute r) { g_apply_routes[r].fetch_add(1, std::memory_order_relaxed); }
+
 int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, const hbec_view* out,
                 uint64_t n_obj, uint64_t shard_len, hipStream_t stream) {
     if (rows <= 0 || n_obj == 0 || shard_len == 0) return HBEC_OK;
@@ -484,8 +489,10 @@ int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, 
     const int force_stream = g_force_stream.load();
     // k > 16 at any alignment: one gf_wide pass instead of accumulate passes
     // (9..12 take gf_odd, 13..16 the round-2 one-pass gf_apply_unaligned)
-    if (!vec && cols > kMaxK && cols <= 256 && pos32_shard(shard_len))
+    if (!vec && cols > kMaxK && cols <= 256 && pos32_shard(shard_len)) {
+        count_apply(kArWide);
         return apply_wide(rows, cols, coeffs, in, out, n_obj, shard_len, stream);
+    }
 
     for (int r0 = 0; r0 < rows; r0 += kMaxR) {
         const int R = std::min(kMaxR, rows - r0);
@@ -496,6 +503,7 @@ int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, 
             int cus = 0, per_cu = 0;
             if (vec && is_packed_shape(K, R, shard_len, c0 > 0, force_stream)) {
                 // short shards: wave tiles across objects (gf_apply_packed)
+                count_apply(kArPacked);
                 rc = device_blocks(dev, OccKind::Packed, K, R, &cus, &per_cu);
                 if (rc) return rc;
                 if (g_blocks_per_cu_override > 0) per_cu = g_blocks_per_cu_override;
@@ -509,6 +517,7 @@ int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, 
                 });
             } else if (vec && !to_rec) {
                 // the pipelined instance's occupancy only for the first column pass
+                count_apply(kArVec);
                 const int pipe = is_pipe_shape(K, R, shard_len, force_stream) && c0 == 0;
                 rc = device_blocks(dev, vec_kind(pipe, force_stream), K, R, &cus, &per_cu);
                 if (rc) return rc;
@@ -526,9 +535,11 @@ int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, 
             } else if (odd_enabled() && cols <= kOddMaxK && pos32_shard(shard_len)) {
                 // any alignment / length: gf_odd (odd.hip), passes of <= 8 inputs,
                 // later ones accumulating into the outputs
+                count_apply(kArOdd);
                 rc = odd_launches(a, K, R, 0, c0 > 0, n_obj, shard_len, nullptr, dev, stream);
             } else {
                 // any alignment: aligned 16-B accesses with in-register shifts (gf_apply_unaligned)
+                count_apply(kArUnaligned);
                 rc = device_blocks(dev, OccKind::Unaligned, K, R, &cus, &per_cu);
                 if (rc) return rc;
                 if (g_unaligned_bpc > 0) per_cu = std::min(per_cu, g_unaligned_bpc);
@@ -1608,6 +1619,15 @@ int hbec_verify_route_stats(hbec_verify_routes* out) {
         auto n = [](hbec::VerifyRoute r) { return hbec::g_verify_routes[r].load(std::memory_order_relaxed); };
         *out = {n(hbec::kVrPacked), n(hbec::kVrPipe),      n(hbec::kVrRecords), n(hbec::kVrOdd),
                 n(hbec::kVrWide),   n(hbec::kVrUnaligned), n(hbec::kVrScratch)};
+        return HBEC_OK;
+    });
+}
+
+int hbec_apply_route_stats(hbec_apply_routes* out) {
+    return hbec::guarded("hbec_apply_route_stats", [&]() -> int {
+        if (!out) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        auto n = [](hbec::ApplyRoute r) { return hbec::g_apply_routes[r].load(std::memory_order_relaxed); };
+        *out = {n(hbec::kArPacked), n(hbec::kArVec), n(hbec::kArOdd), n(hbec::kArUnaligned), n(hbec::kArWide)};
         return HBEC_OK;
     });
 }

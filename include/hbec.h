@@ -472,6 +472,18 @@ typedef struct hbec_verify_routes {
     uint64_t packed, pipe, records, odd, wide, unaligned, scratch;
 } hbec_verify_routes;
 int hbec_verify_route_stats(hbec_verify_routes* out);
+/* Passes since load of the generic apply behind hbec_encode_batch,
+ * hbec_reconstruct_batch, hbec_apply_batch and the per-stripe routes (one pass =
+ * up to 4 output rows from up to 16 inputs), by the branch that coded them:
+ * packed = gf_apply_packed, vec = the 16-B-aligned kernels, odd = the gf_odd
+ * families at any alignment (told apart by hbec_odd_path_stats; 16-B-aligned
+ * shapes sent to the record kernels count here), unaligned = gf_apply_unaligned,
+ * wide = gf_wide (k > 16 at any alignment, one count per call).  Calls with
+ * nothing to do count nowhere. */
+typedef struct hbec_apply_routes {
+    uint64_t packed, vec, odd, unaligned, wide;
+} hbec_apply_routes;
+int hbec_apply_route_stats(hbec_apply_routes* out);
 
 /* Odd-shard guard bands (the <= 64 head and tail bytes of each shard the main
  * kernels' 16-B frame does not store): launches since load of the separate

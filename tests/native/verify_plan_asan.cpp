@@ -100,6 +100,10 @@ static int arguments() {
     CHECK(hbec_verify_route_stats(nullptr) == HBEC_ERR_INVALID_ARG);
     CHECK(hbec_verify_route_stats(&vr) == HBEC_OK);
     CHECK(vr.packed + vr.pipe + vr.records + vr.odd + vr.wide + vr.unaligned + vr.scratch == 0);  // nothing reached a route
+    hbec_apply_routes ar;
+    CHECK(hbec_apply_route_stats(nullptr) == HBEC_ERR_INVALID_ARG);
+    CHECK(hbec_apply_route_stats(&ar) == HBEC_OK);
+    CHECK(ar.packed + ar.vec + ar.odd + ar.unaligned + ar.wide == 0);  // nothing reached a pass
     CHECK(hbec_verify_plan_tile_bytes(8) == (int)hbec::kVpTile);
     for (hbec_plan* p : {ps, po, p0, pm}) hbec_plan_free(p);
     hbec_free(c42);

@@ -113,6 +113,11 @@ def test_stats_and_tile_bytes_answer():
     r0 = B.verify_route_stats()
     assert list(r0) == ["packed", "pipe", "records", "odd", "wide", "unaligned", "scratch"]
     assert B.verify_route_stats() == r0  # nothing was verified here
+    assert L.hbec_apply_route_stats(None) == N.ERR_INVALID_ARG
+    assert "null" in N.last_error()
+    a0 = B.apply_route_stats()
+    assert list(a0) == ["packed", "vec", "odd", "unaligned", "wide"]
+    assert B.apply_route_stats() == a0  # nothing was coded here
     s0 = B.verify_plan_stats()
     assert set(s0) == {"plan_launches", "per_stripe_calls"}
     assert B.verify_plan_stats() == s0  # nothing was launched here
