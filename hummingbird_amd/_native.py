@@ -78,6 +78,7 @@ _SIG = [
     ("hbec_reconstruct_batch_mixed", C.c_int,
      [_P, C.POINTER(View), _U8P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64, C.c_int, _P]),
     ("hbec_mixed_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_mixed_walk_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_set_mixed_chunk_tiles", C.c_int, [C.c_uint64]),
     ("hbec_md5_batch", C.c_int, [C.POINTER(View), C.c_int, C.c_uint64, C.c_uint64, _P, _P]),
     ("hbec_md5_list", C.c_int, [C.POINTER(_P), C.POINTER(C.c_uint64), C.c_uint64, _P, _P]),

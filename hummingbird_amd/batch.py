@@ -95,6 +95,16 @@ def mixed_stats():
     return {"mixed": a.value, "runs": b.value}
 
 
+def mixed_walk_stats():
+    """Mixed-kernel launches since load by the walk of their waves
+    (hbec_mixed_walk_stats): a contiguous run of the sorted entry list per wave
+    (`contiguous`) or grid-stride (`grid_stride`), and the launches whose waves
+    took two tiles or more (`looping`)."""
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_mixed_walk_stats(C.byref(a), C.byref(b), C.byref(c)))
+    return {"contiguous": a.value, "grid_stride": b.value, "looping": c.value}
+
+
 def set_mixed_chunk_tiles(tiles: int) -> None:
     """Test hook: mixed-kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_mixed_chunk_tiles(int(tiles)))

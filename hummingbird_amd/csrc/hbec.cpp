@@ -949,6 +949,9 @@ static const DirectFns kDirect = {direct_encode, direct_reconstruct};
 // Reconstruct with an erasure pattern per object (gf_apply_mixed, mixed.hip)
 // ---------------------------------------------------------------------------
 static std::atomic<uint64_t> g_mixed_launches{0}, g_run_launches{0};
+// gf_apply_mixed launches by the walk mixed_contiguous chose, and those whose
+// waves take two tiles or more (hbec_mixed_walk_stats)
+static std::atomic<uint64_t> g_mixed_contig_launches{0}, g_mixed_stride_launches{0}, g_mixed_looping{0};
 // test hook (hbec_set_mixed_chunk_tiles): tiles per launch of the mixed kernel
 static std::atomic<uint64_t> g_mixed_chunk_override{0};
 // How a launch's waves walk its tiles.  Grid-stride (gf_apply_stripes' walk)
@@ -1082,6 +1085,8 @@ static int mixed_fast(const hbec_codec* c, const hbec_view* views, std::vector<M
             a.wave_step = contig ? a.iters : 1u;
             a.iter_step = contig ? 1u : (uint32_t)waves;
             g_mixed_launches.fetch_add(1, std::memory_order_relaxed);
+            (contig ? g_mixed_contig_launches : g_mixed_stride_launches).fetch_add(1, std::memory_order_relaxed);
+            if (a.iters >= 2) g_mixed_looping.fetch_add(1, std::memory_order_relaxed);
             e = launch_mixed(k, r, a, d_recs, d_ents + e0, grid, stream);
         }
     }
@@ -1342,6 +1347,16 @@ int hbec_mixed_stats(uint64_t* mixed_launches, uint64_t* run_launches) {
         if (!mixed_launches || !run_launches) return fail(HBEC_ERR_INVALID_ARG, "null argument");
         *mixed_launches = g_mixed_launches.load(std::memory_order_relaxed);
         *run_launches = g_run_launches.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_mixed_walk_stats(uint64_t* contiguous, uint64_t* grid_stride, uint64_t* looping) {
+    return hbec::guarded("hbec_mixed_walk_stats", [&]() -> int {
+        if (!contiguous || !grid_stride || !looping) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *contiguous = g_mixed_contig_launches.load(std::memory_order_relaxed);
+        *grid_stride = g_mixed_stride_launches.load(std::memory_order_relaxed);
+        *looping = g_mixed_looping.load(std::memory_order_relaxed);
         return HBEC_OK;
     });
 }

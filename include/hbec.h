@@ -184,6 +184,10 @@ int hbec_reconstruct_batch_mixed(hbec_codec* codec, const hbec_view* views, cons
                                  uint64_t shard_len, int data_only, void* hip_stream);
 /* launches since load: of the mixed kernel, and of per-run launches of the single-pattern path */
 int hbec_mixed_stats(uint64_t* mixed_launches, uint64_t* run_launches);
+/* mixed-kernel launches since load by how their waves walk the launch's tiles
+ * (a contiguous run of the sorted list per wave, or grid-stride), and those
+ * whose waves take two tiles or more */
+int hbec_mixed_walk_stats(uint64_t* contiguous, uint64_t* grid_stride, uint64_t* looping);
 /* test hook, as hbec_set_odd_chunk_tiles: tiles per launch of the mixed kernel (0 = default) */
 int hbec_set_mixed_chunk_tiles(uint64_t tiles);
 

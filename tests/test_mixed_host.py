@@ -59,6 +59,12 @@ def test_null_arguments():
     assert L.hbec_mixed_stats(None, C.byref(a)) == N.ERR_INVALID_ARG
     assert L.hbec_mixed_stats(C.byref(a), None) == N.ERR_INVALID_ARG
     assert N.last_error()
+    b, c = C.c_uint64(), C.c_uint64()
+    assert L.hbec_mixed_walk_stats(None, C.byref(b), C.byref(c)) == N.ERR_INVALID_ARG
+    assert L.hbec_mixed_walk_stats(C.byref(a), None, C.byref(c)) == N.ERR_INVALID_ARG
+    assert L.hbec_mixed_walk_stats(C.byref(a), C.byref(b), None) == N.ERR_INVALID_ARG
+    assert "null" in N.last_error()
+    assert L.hbec_mixed_walk_stats(C.byref(a), C.byref(b), C.byref(c)) == N.HBEC_OK
 
 
 def test_pattern_count_and_index_errors():
