@@ -27,6 +27,15 @@ ERR_UNEXPECTED_EOF = -10
 ERR_IO = -11
 ERR_SCHEME = -12
 
+# bits of a word of hbec_locate_plan_mixed, and what hbec_locate_decode returns
+LOC_BAD = 0x80000000
+LOC_SKIPPED = 0x40000000
+LOC_NOTHING = 0x20000000
+LOC_CLEAN = -1
+LOC_AMBIGUOUS = -2
+LOC_MULTIPLE = -3
+LOC_UNCHECKED = -4
+
 
 class View(C.Structure):
     _fields_ = [("base", C.c_void_p), ("obj_stride", C.c_uint64)]
@@ -113,6 +122,11 @@ _SIG = [
     ("hbec_verify_mixed_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_verify_mixed_plan_tile_bytes", C.c_int, []),
     ("hbec_set_verify_mixed_plan_chunk_tiles", C.c_int, [C.c_uint64]),
+    ("hbec_locate_plan_mixed", C.c_int, [_P, _P, _U8P, C.c_uint32, C.POINTER(C.c_uint32), _P, _P, _P]),
+    ("hbec_locate_decode", C.c_int, [C.c_int, C.c_int, _U8P, C.c_uint32]),
+    ("hbec_locate_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_locate_plan_tile_bytes", C.c_int, []),
+    ("hbec_set_locate_plan_chunk_tiles", C.c_int, [C.c_uint64]),
     ("hbec_verify_host", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64, _U8P]),
     ("hbec_encode_host", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64]),
     ("hbec_host_alloc", C.c_int, [C.c_size_t, C.POINTER(_P)]),

@@ -247,6 +247,85 @@ class StripePlan:
             self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
             pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(flags.data_ptr()), _stream_ptr(stream)))
 
+    def locate_mixed(self, present, where, flags=None, stream=None):
+        """Name the corrupt shard of every inconsistent entry: ``present`` is an
+        [n, k+m] array as in verify_mixed (None: every shard present), ``where``
+        a caller-zeroed 32-bit CUDA tensor with one word per entry that is ORed
+        into: LOC_BAD, LOC_SKIPPED, LOC_NOTHING and, in bits 0..15, the present
+        shards that cannot alone explain some inconsistent byte
+        (hbec_locate_plan_mixed; decode with locate_decode).  ``flags``: the
+        tensor verify_mixed filled under the same masks; only entries with bit 0
+        set are read.  None: every entry is examined.  Read-only apart from
+        ``where``; queued on the stream."""
+        import numpy as np
+        import torch
+
+        n = self.enc.DataShards + self.enc.ParityShards
+        for name, t in (("where", where), ("flags", flags)):
+            if t is None and name == "flags":
+                continue
+            if t.dtype != torch.uint32 and t.dtype != torch.int32:
+                raise ValueError(f"{name} must be a 32-bit integer tensor")
+            if not t.is_cuda or not t.is_contiguous() or t.numel() < self._n:
+                raise ValueError(f"{name} must be a contiguous CUDA tensor with one entry per stripe")
+        if flags is not None and flags.data_ptr() == where.data_ptr() and self._n:
+            raise ValueError("where must not alias flags")
+        p = np.ones((self._n, n), bool) if present is None else np.asarray(present) != 0
+        if p.ndim != 2 or p.shape[0] != self._n or p.shape[1] != n:
+            raise ValueError("present must be [n_stripes, k+m]")
+        if self._n == 0:
+            patterns, pattern_of = p.astype(np.uint8), np.zeros(0, np.uint32)
+        else:
+            patterns, pattern_of = np.unique(p.astype(np.uint8), axis=0, return_inverse=True)
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        pattern_of = np.ascontiguousarray(pattern_of.reshape(-1), dtype=np.uint32)
+        check(N.lib().hbec_locate_plan_mixed(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)),
+            None if flags is None else C.c_void_p(flags.data_ptr()), C.c_void_p(where.data_ptr()),
+            _stream_ptr(stream)))
+
+
+def locate_decode(k: int, m: int, present, where_array):
+    """The shard every word of ``where_array`` names (hbec_locate_decode; host
+    only): an int array of shard indices, or LOC_CLEAN, LOC_AMBIGUOUS,
+    LOC_MULTIPLE, LOC_UNCHECKED.  ``present``: [n, k+m] masks as given to
+    locate_mixed, one mask for all, or None (every shard present)."""
+    import numpy as np
+
+    w = np.asarray(where_array).reshape(-1).astype(np.int64) & 0xFFFFFFFF
+    p = np.ones((1, k + m), np.uint8) if present is None else np.asarray(present) != 0
+    p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.uint8)
+    if p.shape[1] != k + m or p.shape[0] not in (1, w.size):
+        raise ValueError("present must be [n, k+m] or one mask of k+m")
+    fn = N.lib().hbec_locate_decode
+    out = np.empty(w.size, np.int64)
+    for i in range(w.size):
+        row = p[i if p.shape[0] > 1 else 0]
+        out[i] = fn(int(k), int(m), row.ctypes.data_as(N._U8P), int(w[i]))
+        if out[i] == N.ERR_INVALID_ARG:
+            raise ValueError("bad (k, m)")
+    return out
+
+
+def locate_plan_stats():
+    """Since load, for StripePlan.locate_mixed: launches of the locate kernel
+    (`kernel_launches`) and entries of a shape it does not take, marked
+    LOC_SKIPPED (`skipped_entries`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_locate_plan_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "skipped_entries": b.value}
+
+
+def locate_plan_tile_bytes() -> int:
+    """Shard bytes per wave tile of the locate kernel."""
+    return int(N.lib().hbec_locate_plan_tile_bytes())
+
+
+def set_locate_plan_chunk_tiles(tiles: int) -> None:
+    """Test hook: locate kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_locate_plan_chunk_tiles(int(tiles)))
+
 
 def verify_plan_stats():
     """Since load: launches of the plan Verify kernels (`plan_launches`) and

@@ -26,6 +26,7 @@
 #include "gf256.h"
 #include "internal.h"
 #include "kernels.h"
+#include "locate.h"
 #include "mixedplan.h"
 #include "vmixed.h"
 #include "vplan.h"
@@ -898,6 +899,89 @@ int verify_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* p
     return HBEC_OK;
 }
 
+// ---- the corrupt shard of every inconsistent stripe (hbec_locate_plan_mixed) ----
+
+std::atomic<uint64_t> g_locplan_launches{0}, g_locplan_skipped{0};
+// test hook (hbec_set_locate_plan_chunk_tiles): tiles per gf_locate_mixed_plan launch
+std::atomic<uint64_t> g_locplan_chunk_override{0};
+
+int locate_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                      const uint32_t* pattern_of, const uint32_t* d_flags, uint32_t* d_where, hipStream_t stream) {
+    std::vector<PlanPattern> pats;  // outs: the checked shards
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    if (!d_where && plan->n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    if (d_where && d_where == d_flags) return fail(HBEC_ERR_INVALID_ARG, "d_where aliases d_flags");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
+    const uint64_t n_src = plan->n_src;
+    std::vector<uint8_t> mask((size_t)n);
+    bool used = false;
+    for (uint32_t p = 0; p < n_patterns; ++p) {
+        PlanPattern& pp = pats[p];
+        if (!pp.uses) continue;
+        used = true;
+        for (int i = 0; i < n; ++i) mask[i] = patterns[(size_t)p * n + i] ? 1 : 0;
+        pp.surv.resize(k);
+        pp.outs.resize(std::max(1, m));
+        pp.rows.resize((size_t)std::max(1, m) * k);
+        int n_checked = 0;
+        rc = hbec_check_rows(codec, mask.data(), pp.surv.data(), pp.outs.data(), &n_checked, pp.rows.data());
+        if (rc) return rc;
+        pp.outs.resize(n_checked);
+        pp.rows.resize((size_t)n_checked * k);
+    }
+    if (!used) return HBEC_OK;  // zero-length entries only
+    rc = mixed_plan_device(plan);
+    if (rc) return rc;
+
+    if (plan->n_mtiles > 0) {
+        // per call, as verify_plan_mixed: the records of the masks with something
+        // to check and one word per source entry, in one buffer
+        std::vector<uint32_t> stage;
+        for (PlanPattern& pp : pats) {
+            if (!pp.uses || pp.outs.empty()) continue;
+            pp.rec = hbec::loc_pattern(stage, k, pp.surv.data(), pp.outs.data(), (int)pp.outs.size(), pp.rows.data());
+        }
+        const size_t rec_words = stage.size();
+        stage.resize(rec_words + (size_t)n_src);
+        uint32_t* words = stage.data() + rec_words;
+        int rmax = 1;  // exactly-k entries alone: any instance sets their bit
+        for (uint64_t i = 0; i < n_src; ++i) {
+            const PlanPattern& pp = pats[pattern_of[i]];
+            const bool kernel = hbec::loc_route(k, m, plan->src[i].shard_len) == hbec::kVmKernel;
+            words[i] = kernel ? hbec::vm_word((int)pp.outs.size(), pp.rec) : 0u;
+            if (kernel) rmax = std::max(rmax, (int)pp.outs.size());
+        }
+        int cus = 0;
+        rc = current_cus(&cus);
+        if (rc) return rc;
+        std::lock_guard<std::mutex> lk(plan->mp_mu);
+        rc = stage_begin(plan, stage, stream);
+        if (rc) return rc;
+        const uint32_t* d_pats = plan->d_mstage;
+        const uint32_t* d_words = d_pats + rec_words;
+        hipError_t e = hipSuccess;
+        const uint64_t hook = g_locplan_chunk_override.load(std::memory_order_relaxed);
+        const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
+        for (uint64_t t0 = 0; t0 < plan->n_mtiles && e == hipSuccess; t0 += chunk) {
+            const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
+            g_locplan_launches.fetch_add(1, std::memory_order_relaxed);
+            e = hbec::launch_locate_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats,
+                                               d_flags, d_where, cus, stream);
+        }
+        rc = stage_end(plan, stream);
+        if (e != hipSuccess) return hip_fail(e, "launch gf_locate_mixed_plan");
+        if (rc) return rc;
+    }
+    // the other route is not examined: said in the entry's word, and counted
+    for (uint32_t i : plan->mp_other) {
+        g_locplan_skipped.fetch_add(1, std::memory_order_relaxed);
+        const hipError_t e = hbec::launch_vm_or(d_where + i, hbec::kLocSkipped, stream);
+        if (e != hipSuccess) return hip_fail(e, "launch gf_vm_or");
+    }
+    return HBEC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1200,6 +1284,43 @@ int hbec_verify_mixed_plan_tile_bytes(void) { return (int)hbec::verify_mixed_pla
 int hbec_set_verify_mixed_plan_chunk_tiles(uint64_t tiles) {
     return hbec::guarded("hbec_set_verify_mixed_plan_chunk_tiles", [&]() -> int {
         g_vmplan_chunk_override.store(tiles, std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+static_assert(HBEC_LOC_BAD == hbec::kLocBad && HBEC_LOC_SKIPPED == hbec::kLocSkipped &&
+                  HBEC_LOC_NOTHING == hbec::kLocNothing && HBEC_LOC_CLEAN == hbec::kLocClean &&
+                  HBEC_LOC_AMBIGUOUS == hbec::kLocAmbiguous && HBEC_LOC_MULTIPLE == hbec::kLocMultiple &&
+                  HBEC_LOC_UNCHECKED == hbec::kLocUnchecked,
+              "include/hbec.h and locate.h disagree");
+
+int hbec_locate_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                           const uint32_t* pattern_of, const uint32_t* d_flags, uint32_t* d_where, void* hip_stream) {
+    return hbec::guarded("hbec_locate_plan_mixed", [&]() -> int {
+        return locate_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, d_flags, d_where,
+                                 static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_locate_decode(int k, int m, const uint8_t* present, uint32_t where) {
+    if (!present || k < 1 || m < 0 || k + m > 256) return HBEC_ERR_INVALID_ARG;
+    return hbec::loc_decode(k, m, present, where);
+}
+
+int hbec_locate_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries) {
+    return hbec::guarded("hbec_locate_plan_stats", [&]() -> int {
+        if (!kernel_launches || !skipped_entries) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *kernel_launches = g_locplan_launches.load(std::memory_order_relaxed);
+        *skipped_entries = g_locplan_skipped.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_locate_plan_tile_bytes(void) { return (int)hbec::locate_plan_tile_bytes(); }
+
+int hbec_set_locate_plan_chunk_tiles(uint64_t tiles) {
+    return hbec::guarded("hbec_set_locate_plan_chunk_tiles", [&]() -> int {
+        g_locplan_chunk_override.store(tiles, std::memory_order_relaxed);
         return HBEC_OK;
     });
 }

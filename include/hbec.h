@@ -367,6 +367,63 @@ int hbec_verify_mixed_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe
 int hbec_verify_mixed_plan_tile_bytes(void);
 /* test hook, as hbec_set_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
 int hbec_set_verify_mixed_plan_chunk_tiles(uint64_t tiles);
+/* Which shard of an inconsistent stripe is the corrupt one: the step between
+ * hbec_verify_plan_mixed ("entry i is inconsistent") and hbec_reconstruct_plan_mixed ("entry
+ * i: do not read shard j"), so that a silently corrupt survivor is not rebuilt into a
+ * silently corrupt shard.  patterns / n_patterns / pattern_of: exactly those of
+ * hbec_verify_plan_mixed, with the same errors, found before anything is queued or written.
+ * d_where: uint32, device, one entry per source entry, zeroed by the caller; it is only ever
+ * ORed into, zero-length entries are never touched, and it must not alias d_flags (which is
+ * read, never written).  Read-only apart from d_where; queued on hip_stream, not waited for.
+ *   bit 31     HBEC_LOC_BAD      some compared byte of the entry is inconsistent
+ *   bit 30     HBEC_LOC_SKIPPED  the entry was not examined (the other route, below)
+ *   bit 29     HBEC_LOC_NOTHING  exactly k shards present: nothing could be checked
+ *   bits 0..15 ruled out         bit j: present shard j cannot alone explain some
+ *                                inconsistent byte position
+ * For entry i with mask patterns[pattern_of[i]], survivors, checked shards and rows are
+ * hbec_check_rows', and a byte position's syndrome is s[q] = stored[checked q] ^ sum_t
+ * rows[q][t] survivor_t.  With r >= 2 checked shards, per position with s != 0: exactly one
+ * non-zero component, at q: the candidate is checked shard q; all r non-zero and s[q]
+ * rows[0][t] == s[0] rows[q][t] for every q: the candidate is survivor t (at most one t
+ * exists); anything else: no candidate.  Every present shard but the candidate is ruled out.
+ * With r = 1 only HBEC_LOC_BAD is set: every present shard stays a candidate, which is the
+ * truth.  At r = 2 the code has distance 3: one corrupt shard is always named, but two
+ * shards corrupt at the same byte position can imitate a third (their syndrome can be any
+ * vector, and k of the plane's 257 lines belong to other columns: about 4 of 257 at 4+2).  At r >= 3 two corrupt shards are never attributed to
+ * one: they leave no candidate (hbec_locate_decode: HBEC_LOC_MULTIPLE).
+ * Filter: entry i is examined when d_flags == NULL or d_flags[i] & 1 (the flags of
+ * hbec_verify_plan_mixed with the same masks); the tiles of every other entry are skipped
+ * and nothing of them is loaded, so a sweep reads only what Verify flagged.  With d_flags ==
+ * NULL the call detects and locates in one pass.  HBEC_LOC_NOTHING and HBEC_LOC_SKIPPED do
+ * not depend on the filter.
+ * k <= 12 with m <= 4 and shards below 2^31 - 64 KiB take one launch (per 2^31 - 1 tiles)
+ * whatever the number of stripes, patterns or checked shards.  Every other non-empty entry
+ * gets HBEC_LOC_SKIPPED and is counted: unlike Verify, this call has no per-stripe fallback
+ * for them.  d_where may be NULL only for a plan built from no entries. */
+#define HBEC_LOC_BAD 0x80000000u
+#define HBEC_LOC_SKIPPED 0x40000000u
+#define HBEC_LOC_NOTHING 0x20000000u
+int hbec_locate_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                           const uint32_t* pattern_of, const uint32_t* d_flags /* may be NULL */,
+                           uint32_t* d_where, void* hip_stream);
+/* The shard a word of d_where names under the entry's mask `present` (k+m bytes; host only,
+ * no GPU): the single present shard not ruled out when HBEC_LOC_BAD is set; HBEC_LOC_CLEAN
+ * when where == 0 (or holds no bit of the above); HBEC_LOC_AMBIGUOUS when HBEC_LOC_BAD is
+ * set and two or more candidates remain (one checked shard only); HBEC_LOC_MULTIPLE when
+ * HBEC_LOC_BAD is set and no candidate remains (more than one shard is wrong);
+ * HBEC_LOC_UNCHECKED for HBEC_LOC_SKIPPED or HBEC_LOC_NOTHING.  A null mask or a bad (k, m):
+ * HBEC_ERR_INVALID_ARG. */
+#define HBEC_LOC_CLEAN (-1)
+#define HBEC_LOC_AMBIGUOUS (-2)
+#define HBEC_LOC_MULTIPLE (-3)
+#define HBEC_LOC_UNCHECKED (-4)
+int hbec_locate_decode(int k, int m, const uint8_t* present, uint32_t where);
+/* launches since load of the locate kernel, and entries given HBEC_LOC_SKIPPED */
+int hbec_locate_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries);
+/* shard bytes per wave tile of the locate kernel */
+int hbec_locate_plan_tile_bytes(void);
+/* test hook, as hbec_set_verify_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
+int hbec_set_locate_plan_chunk_tiles(uint64_t tiles);
 
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
