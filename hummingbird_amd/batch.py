@@ -247,6 +247,38 @@ class StripePlan:
             self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
             pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(flags.data_ptr()), _stream_ptr(stream)))
 
+    def repair_mixed(self, present, flags, data_only=False, stream=None):
+        """verify_mixed and reconstruct_mixed in one pass that reads every
+        entry's k survivors once: the missing shards of entry i are rebuilt
+        from its first k present shards (missing data shards only with
+        data_only) and its other present shards are checked against what those
+        k imply; flags[i] |= 1 on a mismatch, |= 2 when exactly k are present
+        (hbec_repair_plan_mixed).  A flagged entry's shards are rebuilt all the
+        same, from survivors that do not agree with the surplus shards: do not
+        commit them; locate_mixed(flags=flags) names the shard to leave out of
+        a second repair.  ``present`` and ``flags`` as in verify_mixed; queued
+        on the stream."""
+        import numpy as np
+        import torch
+
+        if flags.dtype != torch.uint32 and flags.dtype != torch.int32:
+            raise ValueError("flags must be a 32-bit integer tensor")
+        if not flags.is_cuda or not flags.is_contiguous() or flags.numel() < self._n:
+            raise ValueError("flags must be a contiguous CUDA tensor with one entry per stripe")
+        p = np.asarray(present) != 0
+        if p.ndim != 2 or p.shape[0] != self._n or p.shape[1] != self.enc.DataShards + self.enc.ParityShards:
+            raise ValueError("present must be [n_stripes, k+m]")
+        if self._n == 0:
+            patterns, pattern_of = p.astype(np.uint8), np.zeros(0, np.uint32)
+        else:
+            patterns, pattern_of = np.unique(p.astype(np.uint8), axis=0, return_inverse=True)
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        pattern_of = np.ascontiguousarray(pattern_of.reshape(-1), dtype=np.uint32)
+        check(N.lib().hbec_repair_plan_mixed(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), int(data_only), C.c_void_p(flags.data_ptr()),
+            _stream_ptr(stream)))
+
     def locate_mixed(self, present, where, flags=None, stream=None):
         """Name the corrupt shard of every inconsistent entry: ``present`` is an
         [n, k+m] array as in verify_mixed (None: every shard present), ``where``
@@ -325,6 +357,25 @@ def locate_plan_tile_bytes() -> int:
 def set_locate_plan_chunk_tiles(tiles: int) -> None:
     """Test hook: locate kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_locate_plan_chunk_tiles(int(tiles)))
+
+
+def repair_plan_stats():
+    """Since load, for StripePlan.repair_mixed: launches of the repair kernel
+    (`kernel_launches`) and entries repaired one at a time for the shapes that
+    kernel does not take (`per_stripe_calls`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_repair_plan_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "per_stripe_calls": b.value}
+
+
+def repair_plan_tile_bytes() -> int:
+    """Shard bytes per wave tile of the repair kernel."""
+    return int(N.lib().hbec_repair_plan_tile_bytes())
+
+
+def set_repair_plan_chunk_tiles(tiles: int) -> None:
+    """Test hook: repair kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_repair_plan_chunk_tiles(int(tiles)))
 
 
 def verify_plan_stats():

@@ -11,7 +11,8 @@
 // (hbec_reconstruct_plan_mixed) runs over per-source-entry records and a tile
 // list of its own, built on first use (mixedplan.h, mixedplan.hip); Verify with
 // a present mask per stripe (hbec_verify_plan_mixed) reads the same records and
-// list (vmixed.h, vmixed.hip).
+// list (vmixed.h, vmixed.hip), and so does the call that rebuilds and checks in
+// one pass (hbec_repair_plan_mixed; repair.h, repair.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +29,7 @@
 #include "kernels.h"
 #include "locate.h"
 #include "mixedplan.h"
+#include "repair.h"
 #include "vmixed.h"
 #include "vplan.h"
 
@@ -686,6 +688,56 @@ int stage_begin(const hbec_plan* plan, const std::vector<uint32_t>& stage, hipSt
     return hip_fail(e, "plan mixed staging");
 }
 
+// The other route of the calls with a pattern per source entry (any k, m, S),
+// one source entry at a time; hbec_reconstruct_plan_mixed, hbec_verify_plan_mixed
+// and hbec_repair_plan_mixed share both.
+// Rebuild: one single-pattern apply of pp's decode rows (pp.outs not empty).
+int reconstruct_other_entry(const hbec_plan* plan, uint32_t i, const PlanPattern& pp, hipStream_t stream) {
+    const int k = plan->k;
+    const hbec::MSrc& s = plan->src[i];
+    auto at = [&](int sh) {
+        const uint64_t addr = sh < k ? s.a + (uint64_t)sh * s.shard_len : s.b + (uint64_t)(sh - k) * s.shard_len;
+        return hbec_view{reinterpret_cast<void*>(addr), 0};
+    };
+    std::vector<hbec_view> vin((size_t)k), vout(pp.outs.size());
+    for (int j = 0; j < k; ++j) vin[j] = at(pp.surv[j]);
+    for (size_t q = 0; q < pp.outs.size(); ++q) vout[q] = at(pp.outs[q]);
+    return hbec::apply_views((int)pp.outs.size(), k, pp.rows.data(), vin.data(), vout.data(), 1, s.shard_len, stream);
+}
+
+// Check (pp.outs: the checked shards): exactly k present, bit 1; all present,
+// the per-stripe Verify; degraded, the checked shards rebuilt from the survivors
+// into scratch and compared with the stored ones.
+int verify_other_entry(hbec_codec* codec, const hbec_plan* plan, uint32_t i, const PlanPattern& pp,
+                       uint32_t* d_flags, int cus, hipStream_t stream) {
+    const int k = plan->k, m = plan->m;
+    const hbec::MSrc& s = plan->src[i];
+    if (pp.outs.empty()) {
+        const hipError_t e = hbec::launch_vm_or(d_flags + i, 2u, stream);
+        return e == hipSuccess ? HBEC_OK : hip_fail(e, "launch gf_vm_or");
+    }
+    if ((int)pp.outs.size() == m)
+        return hbec::verify_other_run(codec, hbec::VOther{s.a, s.b, s.shard_len, i}, d_flags, stream);
+    auto at = [&](int sh) {
+        return sh < k ? s.a + (uint64_t)sh * s.shard_len : s.b + (uint64_t)(sh - k) * s.shard_len;
+    };
+    void* scratch = nullptr;
+    int rc = hbec::scratch_alloc(pp.outs.size() * (size_t)s.shard_len, stream, &scratch);
+    if (rc) return rc;
+    uint8_t* rebuilt = static_cast<uint8_t*>(scratch);
+    std::vector<hbec_view> vin((size_t)k), vout(pp.outs.size());
+    for (int j = 0; j < k; ++j) vin[j] = hbec_view{reinterpret_cast<void*>(at(pp.surv[j])), 0};
+    for (size_t q = 0; q < pp.outs.size(); ++q) vout[q] = hbec_view{rebuilt + q * (size_t)s.shard_len, 0};
+    rc = hbec::apply_views((int)pp.outs.size(), k, pp.rows.data(), vin.data(), vout.data(), 1, s.shard_len, stream);
+    hipError_t e = hipSuccess;
+    for (size_t q = 0; q < pp.outs.size() && !rc && e == hipSuccess; ++q)
+        e = hbec::launch_vm_compare(rebuilt + q * (size_t)s.shard_len, reinterpret_cast<const void*>(at(pp.outs[q])),
+                                    s.shard_len, d_flags + i, cus, stream);
+    hbec::scratch_free(scratch, stream);
+    if (rc) return rc;
+    return e == hipSuccess ? HBEC_OK : hip_fail(e, "launch gf_vm_compare");
+}
+
 int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
                            const uint32_t* pattern_of, bool data_only, hipStream_t stream) {
     std::vector<PlanPattern> pats;
@@ -765,20 +817,11 @@ int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8
         if (rc) return rc;
     }
     // the other route: one single-pattern apply per stripe (any k, m, S)
-    std::vector<hbec_view> vin((size_t)k), vout;
     for (uint32_t i : plan->mp_other) {
         const PlanPattern& pp = pats[pattern_of[i]];
         if (pp.outs.empty()) continue;
-        const hbec::MSrc& s = plan->src[i];
-        auto at = [&](int sh) {
-            const uint64_t addr = sh < k ? s.a + (uint64_t)sh * s.shard_len : s.b + (uint64_t)(sh - k) * s.shard_len;
-            return hbec_view{reinterpret_cast<void*>(addr), 0};
-        };
-        vout.resize(pp.outs.size());
-        for (int j = 0; j < k; ++j) vin[j] = at(pp.surv[j]);
-        for (size_t q = 0; q < pp.outs.size(); ++q) vout[q] = at(pp.outs[q]);
         g_mplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
-        rc = hbec::apply_views((int)pp.outs.size(), k, pp.rows.data(), vin.data(), vout.data(), 1, s.shard_len, stream);
+        rc = reconstruct_other_entry(plan, i, pp, stream);
         if (rc) return rc;
     }
     return HBEC_OK;
@@ -859,42 +902,118 @@ int verify_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* p
         if (e != hipSuccess) return hip_fail(e, "launch gf_verify_mixed_plan");
         if (rc) return rc;
     }
-    // the other route, one stripe at a time (any k, m, S): all present, the
-    // per-stripe Verify; degraded, the checked shards rebuilt from the survivors
-    // into scratch and compared with the stored ones
-    std::vector<hbec_view> vin((size_t)k), vout;
+    // the other route, one stripe at a time (any k, m, S)
     for (uint32_t i : plan->mp_other) {
-        const PlanPattern& pp = pats[pattern_of[i]];
-        const hbec::MSrc& s = plan->src[i];
         g_vmplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
-        if (pp.outs.empty()) {
-            const hipError_t e = hbec::launch_vm_or(d_flags + i, 2u, stream);
-            if (e != hipSuccess) return hip_fail(e, "launch gf_vm_or");
-            continue;
-        }
-        if ((int)pp.outs.size() == m) {
-            rc = hbec::verify_other_run(codec, hbec::VOther{s.a, s.b, s.shard_len, i}, d_flags, stream);
-            if (rc) return rc;
-            continue;
-        }
-        auto at = [&](int sh) {
-            return sh < k ? s.a + (uint64_t)sh * s.shard_len : s.b + (uint64_t)(sh - k) * s.shard_len;
-        };
-        void* scratch = nullptr;
-        rc = hbec::scratch_alloc(pp.outs.size() * (size_t)s.shard_len, stream, &scratch);
+        rc = verify_other_entry(codec, plan, i, pats[pattern_of[i]], d_flags, cus, stream);
         if (rc) return rc;
-        uint8_t* rebuilt = static_cast<uint8_t*>(scratch);
-        vout.resize(pp.outs.size());
-        for (int j = 0; j < k; ++j) vin[j] = hbec_view{reinterpret_cast<void*>(at(pp.surv[j])), 0};
-        for (size_t q = 0; q < pp.outs.size(); ++q) vout[q] = hbec_view{rebuilt + q * (size_t)s.shard_len, 0};
-        rc = hbec::apply_views((int)pp.outs.size(), k, pp.rows.data(), vin.data(), vout.data(), 1, s.shard_len, stream);
+    }
+    return HBEC_OK;
+}
+
+// ---- rebuild the missing shards and check the surplus ones (hbec_repair_plan_mixed) ----
+
+std::atomic<uint64_t> g_rplan_launches{0}, g_rplan_per_stripe{0};
+// test hook (hbec_set_repair_plan_chunk_tiles): tiles per gf_repair_mixed_plan launch
+std::atomic<uint64_t> g_rplan_chunk_override{0};
+
+int repair_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                      const uint32_t* pattern_of, bool data_only, uint32_t* d_flags, hipStream_t stream) {
+    std::vector<PlanPattern> outp;  // outs: the shards to rebuild (reconstruct_plan_mixed's)
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, outp);
+    if (rc) return rc;
+    if (!d_flags && plan->n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
+    const uint64_t n_src = plan->n_src;
+    std::vector<PlanPattern> chkp(n_patterns);  // outs: the checked shards (verify_plan_mixed's)
+    std::vector<uint8_t> mask((size_t)n);
+    bool used = false;
+    for (uint32_t p = 0; p < n_patterns; ++p) {
+        PlanPattern &po = outp[p], &pc = chkp[p];
+        if (!po.uses) continue;
+        used = true;
+        int n_present = 0, data_present = 0;
+        for (int i = 0; i < n; ++i) {
+            mask[i] = patterns[(size_t)p * n + i] ? 1 : 0;
+            n_present += mask[i];
+            if (i < k) data_present += mask[i];
+        }
+        pc.surv.resize(k);
+        pc.outs.resize(std::max(1, m));
+        pc.rows.resize((size_t)std::max(1, m) * k);
+        int n_checked = 0;
+        rc = hbec_check_rows(codec, mask.data(), pc.surv.data(), pc.outs.data(), &n_checked, pc.rows.data());
+        if (rc) return rc;
+        pc.outs.resize(n_checked);
+        pc.rows.resize((size_t)n_checked * k);
+        if (n_present == n || (data_only && data_present == k)) continue;  // nothing to rebuild
+        po.surv.resize(k);
+        po.outs.resize(n);
+        po.rows.resize((size_t)n * k);
+        int n_out = 0;
+        rc = hbec_decode_rows(codec, mask.data(), data_only ? 1 : 0, po.surv.data(), po.outs.data(), &n_out,
+                              po.rows.data());
+        if (rc) return rc;
+        po.outs.resize(n_out);
+        po.rows.resize((size_t)n_out * k);
+    }
+    if (!used) return HBEC_OK;  // zero-length entries only
+    rc = mixed_plan_device(plan);
+    if (rc) return rc;
+    int cus = 0;
+    rc = current_cus(&cus);
+    if (rc) return rc;
+
+    if (plan->n_mtiles > 0) {
+        // per call, as verify_plan_mixed: the records of the masks with a shard
+        // to rebuild or to check and one word per source entry, in one buffer
+        std::vector<uint32_t> stage;
+        for (uint32_t p = 0; p < n_patterns; ++p) {
+            PlanPattern &po = outp[p], &pc = chkp[p];
+            if (!po.uses || po.outs.size() + pc.outs.size() == 0) continue;
+            po.rec = hbec::rp_pattern(stage, k, pc.surv.data(), po.outs.data(), (int)po.outs.size(), po.rows.data(),
+                                      pc.outs.data(), (int)pc.outs.size(), pc.rows.data());
+        }
+        const size_t rec_words = stage.size();
+        stage.resize(rec_words + (size_t)n_src);
+        uint32_t* words = stage.data() + rec_words;
+        int rmax = 1;  // exactly-k entries with nothing to rebuild alone: any instance sets their bit
+        for (uint64_t i = 0; i < n_src; ++i) {
+            const PlanPattern &po = outp[pattern_of[i]], &pc = chkp[pattern_of[i]];
+            const bool kernel = hbec::rp_route(k, m, plan->src[i].shard_len) == hbec::kVmKernel;
+            words[i] = kernel ? hbec::rp_word((int)po.outs.size(), (int)pc.outs.size(), po.rec) : 0u;
+            if (kernel) rmax = std::max(rmax, (int)(po.outs.size() + pc.outs.size()));
+        }
+        std::lock_guard<std::mutex> lk(plan->mp_mu);
+        rc = stage_begin(plan, stage, stream);
+        if (rc) return rc;
+        const uint32_t* d_pats = plan->d_mstage;
+        const uint32_t* d_words = d_pats + rec_words;
         hipError_t e = hipSuccess;
-        for (size_t q = 0; q < pp.outs.size() && !rc && e == hipSuccess; ++q)
-            e = hbec::launch_vm_compare(rebuilt + q * (size_t)s.shard_len, reinterpret_cast<const void*>(at(pp.outs[q])),
-                                        s.shard_len, d_flags + i, cus, stream);
-        hbec::scratch_free(scratch, stream);
+        const uint64_t hook = g_rplan_chunk_override.load(std::memory_order_relaxed);
+        const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
+        // one launch per chunk of the list, of the instance for the largest count
+        // of rows (outputs and checked shards together) in use
+        for (uint64_t t0 = 0; t0 < plan->n_mtiles && e == hipSuccess; t0 += chunk) {
+            const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
+            g_rplan_launches.fetch_add(1, std::memory_order_relaxed);
+            e = hbec::launch_repair_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats,
+                                               d_flags, cus, stream);
+        }
+        rc = stage_end(plan, stream);
+        if (e != hipSuccess) return hip_fail(e, "launch gf_repair_mixed_plan");
         if (rc) return rc;
-        if (e != hipSuccess) return hip_fail(e, "launch gf_vm_compare");
+    }
+    // the other route, one stripe at a time (any k, m, S): what verify_plan_mixed
+    // does with the entry, then what reconstruct_plan_mixed does with it
+    for (uint32_t i : plan->mp_other) {
+        g_rplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
+        rc = verify_other_entry(codec, plan, i, chkp[pattern_of[i]], d_flags, cus, stream);
+        if (rc) return rc;
+        const PlanPattern& po = outp[pattern_of[i]];
+        if (po.outs.empty()) continue;
+        rc = reconstruct_other_entry(plan, i, po, stream);
+        if (rc) return rc;
     }
     return HBEC_OK;
 }
@@ -1284,6 +1403,32 @@ int hbec_verify_mixed_plan_tile_bytes(void) { return (int)hbec::verify_mixed_pla
 int hbec_set_verify_mixed_plan_chunk_tiles(uint64_t tiles) {
     return hbec::guarded("hbec_set_verify_mixed_plan_chunk_tiles", [&]() -> int {
         g_vmplan_chunk_override.store(tiles, std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_repair_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                           const uint32_t* pattern_of, int data_only, uint32_t* d_flags, void* hip_stream) {
+    return hbec::guarded("hbec_repair_plan_mixed", [&]() -> int {
+        return repair_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, data_only != 0, d_flags,
+                                 static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_repair_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
+    return hbec::guarded("hbec_repair_plan_stats", [&]() -> int {
+        if (!kernel_launches || !per_stripe_calls) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *kernel_launches = g_rplan_launches.load(std::memory_order_relaxed);
+        *per_stripe_calls = g_rplan_per_stripe.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_repair_plan_tile_bytes(void) { return (int)hbec::repair_plan_tile_bytes(); }
+
+int hbec_set_repair_plan_chunk_tiles(uint64_t tiles) {
+    return hbec::guarded("hbec_set_repair_plan_chunk_tiles", [&]() -> int {
+        g_rplan_chunk_override.store(tiles, std::memory_order_relaxed);
         return HBEC_OK;
     });
 }

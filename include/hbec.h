@@ -424,6 +424,48 @@ int hbec_locate_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries)
 int hbec_locate_plan_tile_bytes(void);
 /* test hook, as hbec_set_verify_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
 int hbec_set_locate_plan_chunk_tiles(uint64_t tiles);
+/* hbec_verify_plan_mixed and hbec_reconstruct_plan_mixed in one pass over the plan: every
+ * stripe's missing shards are rebuilt and its surplus present shards are checked while its k
+ * survivors are read once ((k + checked + rebuilt) S bytes moved per stripe instead of
+ * (2k + checked + rebuilt) S).  This is the call a repair sweep makes by default: "rebuild,
+ * and tell me which results I must not commit" (ecReconstruct rebuilds from the first k
+ * shards it can get, ecutils.go:94-111, so a silently corrupt survivor becomes a silently
+ * corrupt rebuilt shard).  patterns / n_patterns / pattern_of / data_only: exactly those of
+ * hbec_reconstruct_plan_mixed; d_flags: exactly that of hbec_verify_plan_mixed.  For entry i
+ * with mask patterns[pattern_of[i]]: survivors = its first k present shards; outputs = its
+ * missing shards, the set hbec_decode_rows(mask, data_only) returns (missing parity is left
+ * untouched and uncomputed with data_only); checked shards and their rows = what
+ * hbec_check_rows(mask) returns.  Every output is written exactly as
+ * hbec_reconstruct_plan_mixed would write it, no other byte of the entry and no byte outside
+ * it is written; d_flags[i] is ORed exactly as hbec_verify_plan_mixed would: |= 1 when some
+ * checked shard differs at some byte from what the survivors imply, |= 2 when exactly k
+ * shards are present.  Buffers and flags after the call are those after
+ * hbec_verify_plan_mixed followed by hbec_reconstruct_plan_mixed with the same arguments, for
+ * every input, codewords or not.  A flagged entry's outputs are still written, from its
+ * first k present shards as Reconstruct would: the flag tells the caller not to commit them.
+ * The sequel for flagged entries is hbec_locate_plan_mixed with these flags, clearing the
+ * named shard in the entry's mask, and a second repair of those entries (for example on a
+ * plan built from them).  An all-present entry is only checked and nothing of it is written.
+ * Zero-length entries are never touched and flag bits the caller had set stay.  Queued on
+ * hip_stream and not waited for.  k <= 12 with m <= 4, at any alignment and shard length,
+ * takes one launch (per 2^31 - 1 tiles) whatever the number of stripes, patterns, rebuilt or
+ * checked shards; other shapes, and shards of 2^31 - 64 KiB bytes or more, take per stripe
+ * what hbec_verify_plan_mixed's per-stripe route does and then what
+ * hbec_reconstruct_plan_mixed's does.  Errors are found before anything is queued, any flag
+ * is ORed or any byte is written, and are hbec_verify_plan_mixed's: a null argument, a plan
+ * built for another (k, m), n_patterns == 0 for a plan with entries or > 65536, an index >=
+ * n_patterns (zero-length entries too): HBEC_ERR_INVALID_ARG; a listed pattern with fewer
+ * than k present, used or not: HBEC_ERR_TOO_FEW_SHARDS.  d_flags may be NULL only for a plan
+ * built from no entries.  Calls of this, hbec_verify_plan_mixed and
+ * hbec_reconstruct_plan_mixed on one plan from different streams take turns. */
+int hbec_repair_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                           const uint32_t* pattern_of, int data_only, uint32_t* d_flags, void* hip_stream);
+/* launches since load of the repair kernel, and entries repaired one at a time on the other route */
+int hbec_repair_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
+/* shard bytes per wave tile of the repair kernel */
+int hbec_repair_plan_tile_bytes(void);
+/* test hook, as hbec_set_verify_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
+int hbec_set_repair_plan_chunk_tiles(uint64_t tiles);
 
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
