@@ -35,6 +35,9 @@ LOC_CLEAN = -1
 LOC_AMBIGUOUS = -2
 LOC_MULTIPLE = -3
 LOC_UNCHECKED = -4
+# flag bits of hbec_heal_plan_mixed beside hbec_repair_plan_mixed's 1 and 2
+HEAL_DONE = 4
+HEAL_UNNAMED = 8
 
 
 class View(C.Structure):
@@ -131,6 +134,10 @@ _SIG = [
     ("hbec_repair_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_repair_plan_tile_bytes", C.c_int, []),
     ("hbec_set_repair_plan_chunk_tiles", C.c_int, [C.c_uint64]),
+    ("hbec_heal_plan_mixed", C.c_int, [_P, _P, _U8P, C.c_uint32, C.POINTER(C.c_uint32), _P, _P, _P]),
+    ("hbec_heal_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_heal_plan_tile_bytes", C.c_int, []),
+    ("hbec_set_heal_plan_chunk_tiles", C.c_int, [C.c_uint64]),
     ("hbec_verify_host", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64, _U8P]),
     ("hbec_encode_host", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64]),
     ("hbec_host_alloc", C.c_int, [C.c_size_t, C.POINTER(_P)]),

@@ -255,8 +255,8 @@ class StripePlan:
         k imply; flags[i] |= 1 on a mismatch, |= 2 when exactly k are present
         (hbec_repair_plan_mixed).  A flagged entry's shards are rebuilt all the
         same, from survivors that do not agree with the surplus shards: do not
-        commit them; locate_mixed(flags=flags) names the shard to leave out of
-        a second repair.  ``present`` and ``flags`` as in verify_mixed; queued
+        commit them; locate_mixed(flags=flags) names the shard to leave out
+        and heal_mixed repairs the entry again without it.  ``present`` and ``flags`` as in verify_mixed; queued
         on the stream."""
         import numpy as np
         import torch
@@ -317,6 +317,44 @@ class StripePlan:
             None if flags is None else C.c_void_p(flags.data_ptr()), C.c_void_p(where.data_ptr()),
             _stream_ptr(stream)))
 
+    def heal_mixed(self, present, where, flags, stream=None):
+        """Act on locate_mixed's answer on this plan, with nothing copied back:
+        every entry whose word of ``where`` names one shard is repaired again
+        with that shard left out of its mask.  The named shard and the missing
+        ones are rewritten from the first k of the others, flags[i] |= HEAL_DONE
+        and repair_mixed's bits for that mask (1: a remaining surplus shard still
+        disagrees, 2: none left to check).  An inconsistent entry with no single
+        shard named (LOC_AMBIGUOUS, LOC_MULTIPLE) gets flags[i] |= HEAL_UNNAMED
+        and is not touched; nor is any other entry (hbec_heal_plan_mixed).
+        ``present``: the masks locate_mixed was given (None: every shard
+        present); ``where``: its words, read only; ``flags`` as in repair_mixed.
+        A sweep is repair_mixed, locate_mixed(flags=flags), heal_mixed, queued
+        on one stream with no synchronisation."""
+        import numpy as np
+        import torch
+
+        n = self.enc.DataShards + self.enc.ParityShards
+        for name, t in (("where", where), ("flags", flags)):
+            if t.dtype != torch.uint32 and t.dtype != torch.int32:
+                raise ValueError(f"{name} must be a 32-bit integer tensor")
+            if not t.is_cuda or not t.is_contiguous() or t.numel() < self._n:
+                raise ValueError(f"{name} must be a contiguous CUDA tensor with one entry per stripe")
+        if flags.data_ptr() == where.data_ptr() and self._n:
+            raise ValueError("where must not alias flags")
+        p = np.ones((self._n, n), bool) if present is None else np.asarray(present) != 0
+        if p.ndim != 2 or p.shape[0] != self._n or p.shape[1] != n:
+            raise ValueError("present must be [n_stripes, k+m]")
+        if self._n == 0:
+            patterns, pattern_of = p.astype(np.uint8), np.zeros(0, np.uint32)
+        else:
+            patterns, pattern_of = np.unique(p.astype(np.uint8), axis=0, return_inverse=True)
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        pattern_of = np.ascontiguousarray(pattern_of.reshape(-1), dtype=np.uint32)
+        check(N.lib().hbec_heal_plan_mixed(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(where.data_ptr()),
+            C.c_void_p(flags.data_ptr()), _stream_ptr(stream)))
+
 
 def locate_decode(k: int, m: int, present, where_array):
     """The shard every word of ``where_array`` names (hbec_locate_decode; host
@@ -376,6 +414,25 @@ def repair_plan_tile_bytes() -> int:
 def set_repair_plan_chunk_tiles(tiles: int) -> None:
     """Test hook: repair kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_repair_plan_chunk_tiles(int(tiles)))
+
+
+def heal_plan_stats():
+    """Since load, for StripePlan.heal_mixed: launches of the heal kernel
+    (`kernel_launches`) and entries of a shape it does not take, left alone
+    (`skipped_entries`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_heal_plan_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "skipped_entries": b.value}
+
+
+def heal_plan_tile_bytes() -> int:
+    """Shard bytes per wave tile of the heal kernel."""
+    return int(N.lib().hbec_heal_plan_tile_bytes())
+
+
+def set_heal_plan_chunk_tiles(tiles: int) -> None:
+    """Test hook: heal kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_heal_plan_chunk_tiles(int(tiles)))
 
 
 def verify_plan_stats():

@@ -12,7 +12,8 @@
 // list of its own, built on first use (mixedplan.h, mixedplan.hip); Verify with
 // a present mask per stripe (hbec_verify_plan_mixed) reads the same records and
 // list (vmixed.h, vmixed.hip), and so does the call that rebuilds and checks in
-// one pass (hbec_repair_plan_mixed; repair.h, repair.hip).
+// one pass (hbec_repair_plan_mixed; repair.h, repair.hip) and the call that
+// rebuilds the shard locate named (hbec_heal_plan_mixed; heal.h, heal.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +26,7 @@
 
 #include "../../include/hbec.h"
 #include "gf256.h"
+#include "heal.h"
 #include "internal.h"
 #include "kernels.h"
 #include "locate.h"
@@ -91,6 +93,18 @@ struct hbec_plan {
     mutable size_t mstage_words = 0;
     mutable hipEvent_t mp_ev = nullptr;  // after the last call's launches, on mp_stream
     mutable hipStream_t mp_stream = nullptr;
+    // hbec_heal_plan_mixed: the records and tables of the last call's masks, on
+    // the host (heal_mu) and on the device (d_heal, under mp_mu and ordered by
+    // mp_ev like d_mstage).  They depend on (k, m) and the masks alone, and a
+    // sweep heals under the masks it has, call after call: the next call with
+    // the same masks inverts no matrix per mask with one shard left out and
+    // stages one index per source entry, nothing else.
+    mutable std::mutex heal_mu;
+    mutable std::vector<uint32_t> heal_bits;
+    mutable std::shared_ptr<const hbec::HealStage> heal_cache;
+    mutable uint32_t* d_heal = nullptr;
+    mutable size_t heal_dev_words = 0;
+    mutable std::shared_ptr<const hbec::HealStage> heal_on_device;  // what d_heal holds
 };
 
 // The gf_odd_rec records of a plan pass depend only on the plan's stripes and
@@ -1101,6 +1115,118 @@ int locate_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* p
     return HBEC_OK;
 }
 
+// ---- rebuild the shard locate named (hbec_heal_plan_mixed) ----
+
+std::atomic<uint64_t> g_healplan_launches{0}, g_healplan_skipped{0};
+// test hook (hbec_set_heal_plan_chunk_tiles): tiles per gf_heal_mixed_plan launch
+std::atomic<uint64_t> g_healplan_chunk_override{0};
+
+int heal_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                    const uint32_t* pattern_of, const uint32_t* d_where, uint32_t* d_flags, hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    if ((!d_where || !d_flags) && plan->n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    if (d_where && d_where == d_flags) return fail(HBEC_ERR_INVALID_ARG, "d_where aliases d_flags");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
+    const uint64_t n_src = plan->n_src;
+    // the masks kernel-route entries use, in order of first use: their rows of the tables
+    std::vector<uint32_t> row_of(n_patterns, hbec::kHealNone), bits;
+    for (uint64_t i = 0; i < n_src; ++i) {
+        if (hbec::heal_route(k, m, plan->src[i].shard_len) != hbec::kVmKernel) continue;
+        uint32_t& row = row_of[pattern_of[i]];
+        if (row != hbec::kHealNone) continue;
+        row = (uint32_t)bits.size();
+        bits.push_back(hbec::heal_mask_bits(n, patterns + (size_t)pattern_of[i] * n));
+    }
+    std::shared_ptr<const hbec::HealStage> hs;
+    if (!bits.empty()) {
+        {
+            std::lock_guard<std::mutex> lk(plan->heal_mu);
+            if (plan->heal_cache && plan->heal_bits == bits) hs = plan->heal_cache;
+        }
+        if (!hs) {
+            auto built = std::make_shared<hbec::HealStage>();
+            int err = HBEC_OK;
+            const bool ok = hbec::heal_build(
+                *built, k, m, bits,
+                [&](const uint8_t* mask, int* surv, int* outs, int* n_out, uint8_t* orows, int* chk, int* n_chk,
+                    uint8_t* crows) {
+                    err = hbec_decode_rows(codec, mask, 0, surv, outs, n_out, orows);
+                    if (!err) err = hbec_check_rows(codec, mask, surv, chk, n_chk, crows);
+                    return err == HBEC_OK;
+                });
+            if (built->overflow)
+                return fail(HBEC_ERR_INVALID_ARG,
+                            "pattern records of the masks with one shard left out exceed 64 MiB");
+            if (!ok) return err ? err : fail(HBEC_ERR_INVALID_ARG, "heal records");
+            built->rec_of.clear();  // only the build needs it
+            hs = built;
+            std::lock_guard<std::mutex> lk(plan->heal_mu);
+            plan->heal_bits = bits;
+            plan->heal_cache = hs;
+        }
+    }
+    rc = mixed_plan_device(plan);
+    if (rc) return rc;
+
+    if (plan->n_mtiles > 0 && !bits.empty()) {
+        const hbec::HealStage& h = *hs;
+        std::vector<uint32_t> index((size_t)n_src);
+        for (uint64_t i = 0; i < n_src; ++i)
+            index[i] = hbec::heal_route(k, m, plan->src[i].shard_len) == hbec::kVmKernel ? row_of[pattern_of[i]]
+                                                                                         : hbec::kHealNone;
+        int cus = 0;
+        rc = current_cus(&cus);
+        if (rc) return rc;
+        std::lock_guard<std::mutex> lk(plan->mp_mu);
+        rc = stage_begin(plan, index, stream);
+        if (rc) return rc;
+        hipError_t e = hipSuccess;
+        if (plan->heal_on_device != hs) {
+            // other masks than the last call's: their records and tables replace those.  This
+            // stream has waited for the last call's launches (stage_begin), so nothing reads them.
+            plan->heal_on_device.reset();
+            if (h.stage.size() > plan->heal_dev_words) {
+                if (plan->d_heal) (void)hipFree(plan->d_heal);
+                plan->d_heal = nullptr;
+                plan->heal_dev_words = 0;
+                const size_t cap = std::max<size_t>(2 * h.stage.size(), 4096);
+                e = hipMalloc(reinterpret_cast<void**>(&plan->d_heal), cap * 4);
+                if (e == hipSuccess) plan->heal_dev_words = cap;
+            }
+            if (e == hipSuccess)
+                e = h.stage.size() * 4 <= kMPlanPutBytes
+                        ? hbec::launch_put_words(plan->d_heal, h.stage.data(), h.stage.size() * 4, stream)
+                        : hipMemcpyAsync(plan->d_heal, h.stage.data(), h.stage.size() * 4, hipMemcpyHostToDevice,
+                                         stream);
+            if (e != hipSuccess) {
+                (void)stage_end(plan, stream);
+                return hip_fail(e, "plan heal records");
+            }
+            plan->heal_on_device = hs;
+        }
+        const uint32_t* d_pats = plan->d_heal;
+        const uint32_t* d_index = plan->d_mstage;
+        const uint64_t hook = g_healplan_chunk_override.load(std::memory_order_relaxed);
+        const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
+        // one launch per chunk of the list; every mask with one shard left out has m rows
+        for (uint64_t t0 = 0; t0 < plan->n_mtiles && e == hipSuccess; t0 += chunk) {
+            const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
+            g_healplan_launches.fetch_add(1, std::memory_order_relaxed);
+            e = hbec::launch_heal_mixed_plan(k, std::max(1, m), plan->d_mrecs, plan->d_mtiles + t0, nt, d_index,
+                                             d_pats + h.words_at, d_pats + h.present_at, d_pats, d_where, d_flags,
+                                             cus, stream);
+        }
+        rc = stage_end(plan, stream);
+        if (e != hipSuccess) return hip_fail(e, "launch gf_heal_mixed_plan");
+        if (rc) return rc;
+    }
+    // the other route is never healed (locate gave it kLocSkipped): counted
+    g_healplan_skipped.fetch_add(plan->mp_other.size(), std::memory_order_relaxed);
+    return HBEC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1297,6 +1423,7 @@ void hbec_plan_free(hbec_plan* plan) {
     if (plan->d_mrecs) (void)hipFree(plan->d_mrecs);
     if (plan->d_mtiles) (void)hipFree(plan->d_mtiles);
     if (plan->d_mstage) (void)hipFree(plan->d_mstage);
+    if (plan->d_heal) (void)hipFree(plan->d_heal);
     if (plan->mp_ev) (void)hipEventDestroy(plan->mp_ev);
     for (uint32_t* l : plan->d_lists)
         if (l) (void)hipFree(l);
@@ -1466,6 +1593,35 @@ int hbec_locate_plan_tile_bytes(void) { return (int)hbec::locate_plan_tile_bytes
 int hbec_set_locate_plan_chunk_tiles(uint64_t tiles) {
     return hbec::guarded("hbec_set_locate_plan_chunk_tiles", [&]() -> int {
         g_locplan_chunk_override.store(tiles, std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+static_assert(HBEC_HEAL_DONE == hbec::kHealDone && HBEC_HEAL_UNNAMED == hbec::kHealUnnamed,
+              "include/hbec.h and heal.h disagree");
+
+int hbec_heal_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                         const uint32_t* pattern_of, const uint32_t* d_where, uint32_t* d_flags, void* hip_stream) {
+    return hbec::guarded("hbec_heal_plan_mixed", [&]() -> int {
+        return heal_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, d_where, d_flags,
+                               static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_heal_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries) {
+    return hbec::guarded("hbec_heal_plan_stats", [&]() -> int {
+        if (!kernel_launches || !skipped_entries) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *kernel_launches = g_healplan_launches.load(std::memory_order_relaxed);
+        *skipped_entries = g_healplan_skipped.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_heal_plan_tile_bytes(void) { return (int)hbec::heal_plan_tile_bytes(); }
+
+int hbec_set_heal_plan_chunk_tiles(uint64_t tiles) {
+    return hbec::guarded("hbec_set_heal_plan_chunk_tiles", [&]() -> int {
+        g_healplan_chunk_override.store(tiles, std::memory_order_relaxed);
         return HBEC_OK;
     });
 }

@@ -443,9 +443,9 @@ int hbec_set_locate_plan_chunk_tiles(uint64_t tiles);
  * hbec_verify_plan_mixed followed by hbec_reconstruct_plan_mixed with the same arguments, for
  * every input, codewords or not.  A flagged entry's outputs are still written, from its
  * first k present shards as Reconstruct would: the flag tells the caller not to commit them.
- * The sequel for flagged entries is hbec_locate_plan_mixed with these flags, clearing the
- * named shard in the entry's mask, and a second repair of those entries (for example on a
- * plan built from them).  An all-present entry is only checked and nothing of it is written.
+ * The sequel for flagged entries is hbec_locate_plan_mixed with these flags and then
+ * hbec_heal_plan_mixed with its words, on this plan and stream with nothing copied back: it
+ * clears the named shard in the entry's mask and repairs the entry again.  An all-present entry is only checked and nothing of it is written.
  * Zero-length entries are never touched and flag bits the caller had set stay.  Queued on
  * hip_stream and not waited for.  k <= 12 with m <= 4, at any alignment and shard length,
  * takes one launch (per 2^31 - 1 tiles) whatever the number of stripes, patterns, rebuilt or
@@ -466,6 +466,48 @@ int hbec_repair_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls
 int hbec_repair_plan_tile_bytes(void);
 /* test hook, as hbec_set_verify_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
 int hbec_set_repair_plan_chunk_tiles(uint64_t tiles);
+/* The step that acts on hbec_locate_plan_mixed's answer, on the same plan and without a host
+ * trip: every entry whose word names one shard is repaired again with that shard left out.
+ * A sweep is hbec_repair_plan_mixed, hbec_locate_plan_mixed(d_flags) and this call, queued on
+ * one plan and one stream with no synchronisation between them.  patterns / n_patterns /
+ * pattern_of: exactly those of hbec_locate_plan_mixed.  d_where: the words that call wrote
+ * under the same masks; read, never written.  d_flags: uint32, device, one entry per source
+ * entry; only ever ORed into; it must not alias d_where.
+ * The named shard of entry i is hbec_locate_decode(k, m, mask, d_where[i]) when that is >= 0:
+ * HBEC_LOC_BAD set, neither HBEC_LOC_SKIPPED nor HBEC_LOC_NOTHING set, and exactly one present
+ * shard not ruled out.
+ * An entry with named shard j ends up exactly as hbec_repair_plan_mixed (data_only = 0) leaves
+ * it with bit j cleared in its mask: survivors are the first k present shards of mask \ {j};
+ * shard j and every missing shard are written, no other byte of the entry and no byte outside
+ * it; shard j is never read; d_flags[i] gets that call's bits for that mask (1: a remaining
+ * surplus shard still disagrees; 2: none is left to check) and HBEC_HEAL_DONE.  If mask \ {j}
+ * has fewer than k present shards (only with words locate did not write) the entry counts as
+ * unnamed.
+ * Every other entry with HBEC_LOC_BAD set and neither of the other two (hbec_locate_decode:
+ * HBEC_LOC_AMBIGUOUS, HBEC_LOC_MULTIPLE): nothing of it is loaded or written; d_flags[i] |=
+ * HBEC_HEAL_UNNAMED.  Every other entry (word 0, HBEC_LOC_NOTHING, HBEC_LOC_SKIPPED, bits of
+ * the caller's own, zero length): untouched, flag included, and nothing of it is loaded.
+ * k <= 12 with m <= 4 and shards below 2^31 - 64 KiB take one launch (per 2^31 - 1 tiles)
+ * whatever the number of stripes, masks or named shards.  Every other non-empty entry is
+ * never healed and is counted (locate gave it HBEC_LOC_SKIPPED): as with locate there is no
+ * per-stripe fallback.  Per call the library stages one pattern record for every distinct
+ * mask with one present shard left out (at most (k + m) per mask in use; equal masks share
+ * one); records are addressed in 22 bits of 16-B units, so a call whose records exceed 64 MiB
+ * (about 65536 such masks at 12+4) returns HBEC_ERR_INVALID_ARG.
+ * Errors are hbec_locate_plan_mixed's, a null d_where or d_flags for a plan with entries, and
+ * d_where == d_flags; all are found before anything is queued, ORed or written.  Queued on
+ * hip_stream and not waited for; calls on one plan take turns with hbec_verify_plan_mixed,
+ * hbec_reconstruct_plan_mixed, hbec_repair_plan_mixed and hbec_locate_plan_mixed. */
+#define HBEC_HEAL_DONE 4u    /* the named shard and the missing shards of the entry were rewritten */
+#define HBEC_HEAL_UNNAMED 8u /* HBEC_LOC_BAD is set but no single present shard is named */
+int hbec_heal_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                         const uint32_t* pattern_of, const uint32_t* d_where, uint32_t* d_flags, void* hip_stream);
+/* launches since load of the heal kernel, and other-route entries left alone */
+int hbec_heal_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries);
+/* shard bytes per wave tile of the heal kernel */
+int hbec_heal_plan_tile_bytes(void);
+/* test hook, as hbec_set_verify_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
+int hbec_set_heal_plan_chunk_tiles(uint64_t tiles);
 
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
