@@ -158,6 +158,10 @@ _SIG = [
     ("hbec_batcher_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_set_force_stream", C.c_int, [C.c_int]),
     ("hbec_set_odd_chunk_tiles", C.c_int, [C.c_uint64]),
+    ("hbec_set_vec_chunk_tiles", C.c_int, [C.c_uint64]),
+    ("hbec_set_vec_grid_cap", C.c_int, [C.c_int]),
+    ("hbec_vec_launch_config", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    ("hbec_pipe2_store_depth", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("hbec_kernel_info", C.c_int,
      [C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("hbec_odd_path_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

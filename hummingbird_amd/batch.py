@@ -539,5 +539,29 @@ def set_odd_chunk_tiles(tiles: int) -> None:
     N.lib().hbec_set_odd_chunk_tiles(int(tiles))
 
 
+def set_vec_chunk_tiles(tiles: int) -> None:
+    """Test hook: aligned strided launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_vec_chunk_tiles(int(tiles)))
+
+
+def set_vec_grid_cap(blocks: int) -> None:
+    """Test hook: at most `blocks` blocks per aligned strided launch (0 = no cap)."""
+    check(N.lib().hbec_set_vec_grid_cap(int(blocks)))
+
+
+def vec_launch_config() -> tuple[int, int]:
+    """(tiles per launch, grid cap) of the aligned strided kernels now in force."""
+    t, g = C.c_uint64(), C.c_int()
+    check(N.lib().hbec_vec_launch_config(C.byref(t), C.byref(g)))
+    return t.value, g.value
+
+
+def pipe2_store_depth(k: int, r: int) -> tuple[int, bool]:
+    """(store depth, run walk) of the pipelined kernel of a k x r pass."""
+    d, run = C.c_int(), C.c_int()
+    check(N.lib().hbec_pipe2_store_depth(k, r, C.byref(d), C.byref(run)))
+    return d.value, bool(run.value)
+
+
 def set_force_stream(on: bool) -> None:
     N.lib().hbec_set_force_stream(1 if on else 0)

@@ -102,6 +102,19 @@ static const uint64_t g_vec_chunk_tiles = [] {
     const long long v = tune_knob("HBEC_VEC_CHUNK_TILES", tune_knob("HBEC_CHUNK_TILES", 0));
     return (uint64_t)(v > 0 ? v : HBEC_VEC_CHUNK_TILES);
 }();
+// test hooks (hbec_set_vec_chunk_tiles, hbec_set_vec_grid_cap): launch size
+// and grid of the aligned strided kernels, so that kilobytes of data walk
+// several rows of a few blocks and cross launch boundaries; 0 = the defaults
+static std::atomic<uint64_t> g_vec_chunk_override{0};
+static std::atomic<int> g_vec_grid_cap{0};
+static uint64_t vec_chunk_tiles() {
+    const uint64_t v = g_vec_chunk_override.load(std::memory_order_relaxed);
+    return v ? v : g_vec_chunk_tiles;
+}
+static int vec_grid_cap(int grid) {
+    const int cap = g_vec_grid_cap.load(std::memory_order_relaxed);
+    return cap > 0 ? std::min(grid, cap) : grid;
+}
 
 // ---------------------------------------------------------------------------
 // Per-device facts (CU count, occupancy per kernel shape)
@@ -526,10 +539,10 @@ int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, 
                 const uint64_t tpo = (shard_len + tile - 1) / tile;
                 const uint64_t wpb = (uint64_t)vec_block_threads(K, R, shard_len, c0 > 0, force_stream) / 64;
                 // keep n_tiles < 2^31 (and <= g_vec_chunk_tiles) per launch: split the batch by objects
-                const uint64_t max_obj = objs_per_launch(g_vec_chunk_tiles, tpo);
+                const uint64_t max_obj = objs_per_launch(vec_chunk_tiles(), tpo);
                 rc = for_object_chunks(a, K, R, n_obj, max_obj, [&](PassArgs& b, uint64_t) {
                     set_tiles(b, tpo);
-                    const int grid = grid_blocks(b.n_tiles, wpb, (uint64_t)cus * per_cu);
+                    const int grid = vec_grid_cap(grid_blocks(b.n_tiles, wpb, (uint64_t)cus * per_cu));
                     return launched(launch_vec(K, R, b, apply_grid_cap(grid), stream, force_stream), "launch gf_apply_vec");
                 });
             } else if (odd_enabled() && cols <= kOddMaxK && pos32_shard(shard_len)) {
@@ -1748,6 +1761,40 @@ int hbec_coalesce_stats(uint64_t* groups, uint64_t* calls) {
 int hbec_set_odd_chunk_tiles(uint64_t tiles) {
     return hbec::guarded("hbec_set_odd_chunk_tiles", [&]() -> int {
         g_odd_chunk_override.store(tiles, std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_set_vec_chunk_tiles(uint64_t tiles) {
+    return hbec::guarded("hbec_set_vec_chunk_tiles", [&]() -> int {
+        if (tiles > (1ull << 31)) return fail(HBEC_ERR_INVALID_ARG, "vec chunk tiles: at most 2^31");
+        g_vec_chunk_override.store(tiles, std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_set_vec_grid_cap(int blocks) {
+    return hbec::guarded("hbec_set_vec_grid_cap", [&]() -> int {
+        if (blocks < 0) return fail(HBEC_ERR_INVALID_ARG, "vec grid cap: negative");
+        g_vec_grid_cap.store(blocks, std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_vec_launch_config(uint64_t* chunk_tiles, int* grid_cap) {
+    return hbec::guarded("hbec_vec_launch_config", [&]() -> int {
+        if (chunk_tiles) *chunk_tiles = vec_chunk_tiles();
+        if (grid_cap) *grid_cap = g_vec_grid_cap.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_pipe2_store_depth(int k, int r, int* depth, int* run) {
+    return hbec::guarded("hbec_pipe2_store_depth", [&]() -> int {
+        if (k < 1 || k > kMaxK || r < 1 || r > kMaxR) return fail(HBEC_ERR_INVALID_ARG, "shape out of range");
+        const int t = k <= HBEC_PIPE_V2_MAXK && r <= 3 ? pipe2_store_depth(k, r) : 1;
+        if (depth) *depth = t;
+        if (run) *run = t > 1 && HBEC_PIPE2_RUN != 0 ? 1 : 0;
         return HBEC_OK;
     });
 }

@@ -79,6 +79,17 @@ int vec_block_threads(int k, int r, uint64_t shard_len, int accumulate, int forc
 // peaks at 3 KiB tiles (tuning.h).
 __host__ __device__ constexpr int pipe_u(int k) { return k <= 4 ? (4 / k) : (k <= 8 ? HBEC_PIPE_U_BIG : 1); }
 
+// Store depth of gf_apply_vec_pipe2 (tuning.h HBEC_PIPE2_STORE_DEPTH): tiles
+// whose outputs a wave stages in registers, T x U x R x 4 per lane and at
+// most 128, before it stores them back to back.  4+2 only: the other
+// instances have no A/B of their own and keep 1.
+__host__ __device__ constexpr int pipe2_store_depth(int k, int r) {
+    return (k == 4 && r == 2 && HBEC_PIPE2_STORE_DEPTH > 1)
+               ? (HBEC_PIPE2_STORE_DEPTH * pipe_u(k) * r * 4 <= 128 ? HBEC_PIPE2_STORE_DEPTH
+                                                                    : 128 / (pipe_u(k) * r * 4))
+               : 1;
+}
+
 // Tile depth of the stripe-plan and verify kernels, from A/B runs on MI355X
 // (profiles/r01_tune_plan_verify.jsonl):
 //  * stripes: pipe_u for K <= 4, 1 KiB for K >= 5 — config 4's 4 KiB objects

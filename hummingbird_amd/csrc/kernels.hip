@@ -274,31 +274,126 @@ __device__ __forceinline__ void pipe2_finish(const u32x4 (&x)[U][K], const PassA
 // tile; a wave past the end re-codes the last tile), so the barrier counts
 // always match.
 
+// Deferred stores (store depth T = pipe2_store_depth(K, R) > 1): the loop
+// runs in groups of T steps.  Each step is the step above, but its U x R
+// results stay in registers with the lane's output addresses (vector
+// registers: T tiles of scalar bases would spill) and live bytes; after
+// the T-th step the group's T x U x R stores are issued back to back.  A
+// group whose T tiles are all full takes the unmasked stores, any other the
+// masked ones (a uniform branch, as pipe2_finish).  The steps left over when
+// the block's step count is no multiple of T store tile by tile.  4+2 with
+// T = 2 and runs of 4 T consecutive tiles per block (HBEC_PIPE2_RUN): 74.4 ->
+// 80.0 % of 8 TB/s (tuning.h, profiles/r07_ab_pipe2_store.jsonl).
+template <int K, int R, int U, int T, bool FULL>
+__device__ __forceinline__ void pipe2_burst(const u32x4 (&acc)[T][U][R], const uint64_t (&dst)[T][R],
+                                            const int32_t (&room)[T]) {
+#pragma unroll
+    for (int s = 0; s < T; ++s)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (FULL || u * 1024 < room[s]) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) st16_addr(dst[s][r] + (uint64_t)u * 1024u, acc[s][u][r]);
+            }
+        }
+}
+
 template <int K, int R>
 __global__ __launch_bounds__(kPipeBlockThreads, 1) void gf_apply_vec_pipe2(PassArgs a) {
     constexpr int U = pipe_u(K);
+    constexpr int T = pipe2_store_depth(K, R);
+    constexpr bool RUN = T > 1 && HBEC_PIPE2_RUN != 0;
     constexpr uint32_t WPB = kPipeBlockThreads / 64;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t nw = gridDim.x * WPB;
     const uint32_t wave0 = __builtin_amdgcn_readfirstlane(xcd_block() * WPB);  // the block's first wave
     const uint32_t dw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t wave = wave0 + dw;
     const uint32_t tpo = a.tiles_per_obj;
     const uint32_t n = a.n_tiles;
-    if (wave0 >= n) return;  // whole blocks only: the loop below has block barriers
+    // The block's step i codes tiles tile_of(i) of its WPB waves.  Grid-stride:
+    // row i of the launch.  RUN: the launch is cut into super-rows of nw T
+    // tiles and the block owns WPB T consecutive tiles of each, WPB per step.
+    // rows = the steps whose first wave's tile exists: block-uniform, as the
+    // loop below has block barriers; a later wave past the end codes the
+    // stand-in tile.
+    const auto tile_of = [&](uint32_t i) -> uint32_t {
+        if (RUN) {
+            const uint32_t q = i / (uint32_t)T;
+            return (q * nw + wave0) * (uint32_t)T + (i - q * (uint32_t)T) * WPB + dw;
+        }
+        return wave0 + dw + i * nw;
+    };
+    uint32_t rows;
+    if (RUN) {
+        const uint32_t span = nw * (uint32_t)T, q = n / span, rem = n - q * span, lo = wave0 * (uint32_t)T;
+        const uint32_t part = rem > lo ? (rem - lo + WPB - 1u) / WPB : 0u;
+        rows = q * (uint32_t)T + (part < (uint32_t)T ? part : (uint32_t)T);
+    } else {
+        rows = wave0 < n ? (n - wave0 + nw - 1u) / nw : 0u;
+    }
+    if (rows == 0) return;  // whole blocks only
+    const uint32_t steps = rows - 1u;  // block-uniform trip count; the last tile has no loads to issue
     const Tables<K, R> tb = load_tables<K, R>(a.tab);
     PipeTile<K, R> cur, nxt;
-    pipe_tile_at<K, R, U>(cur, a, wave, n, tpo);
+    pipe_tile_at<K, R, U>(cur, a, tile_of(0), n, tpo);
     u32x4 x[U][K];
     pipe2_load<K, R, U>(x, cur, lane);
-    pipe_tile_at<K, R, U>(nxt, a, wave + nw, n, tpo);
-    for (uint32_t b0 = wave0 + nw; b0 < n; b0 += nw) {  // block-uniform trip count
+    pipe_tile_at<K, R, U>(nxt, a, tile_of(1), n, tpo);
+    uint32_t i = 0;
+    if constexpr (T > 1) {
+        for (uint32_t g = steps / (uint32_t)T; g > 0; --g) {
+            u32x4 acc[T][U][R];
+            uint64_t dst[T][R];  // the lane's output addresses
+            int32_t room[T];     // live bytes from the lane's first byte on (<= 0: the lane stores nothing)
+            bool full = true;
+#pragma unroll
+            for (int s = 0; s < T; ++s) {
+                u32x4 y[U][K];
+                pipe2_load<K, R, U>(y, nxt, lane);
+                if (K <= 4) __builtin_amdgcn_s_sleep(HBEC_PIPE2_SLEEP);
+                __builtin_amdgcn_s_barrier();
+                // the arithmetic shares a basic block with the loads here (no
+                // store branch between them): keep it behind the barrier
+                __builtin_amdgcn_sched_barrier(0);
+                PipeTile<K, R> after;
+                pipe_tile_at<K, R, U>(after, a, tile_of(i + 2u), n, tpo);
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) acc[s][u][r] = u32x4{0, 0, 0, 0};
+                    gf_dot<K, R>(acc[s][u], x[u], a.tab, tb);
+                }
+#pragma unroll
+                for (int r = 0; r < R; ++r) dst[s][r] = cur.out[r] + (uint64_t)lane * 16u;
+                room[s] = (int32_t)cur.live - (int32_t)(lane * 16u);
+                full = full && cur.live >= (uint32_t)U * 1024u;
+                // the results are final here, not sunk into the store branches below
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int r = 0; r < R; ++r) asm volatile("" : "+v"(acc[s][u][r]));
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int j = 0; j < K; ++j) x[u][j] = y[u][j];
+                cur = nxt;
+                nxt = after;
+                ++i;
+            }
+            if (full)
+                pipe2_burst<K, R, U, T, true>(acc, dst, room);
+            else
+                pipe2_burst<K, R, U, T, false>(acc, dst, room);
+        }
+    }
+    for (; i < steps; ++i) {
         u32x4 y[U][K];
         pipe2_load<K, R, U>(y, nxt, lane);
         if (K <= 4) __builtin_amdgcn_s_sleep(HBEC_PIPE2_SLEEP);
         __builtin_amdgcn_s_barrier();
         PipeTile<K, R> after;
-        pipe_tile_at<K, R, U>(after, a, b0 + dw + nw, n, tpo);
+        pipe_tile_at<K, R, U>(after, a, tile_of(i + 2u), n, tpo);
         pipe2_finish<K, R, U>(x, a, tb, cur, lane);
 #pragma unroll
         for (int u = 0; u < U; ++u)

@@ -26,7 +26,24 @@
 #define HBEC_PIPE_SLEEP 6  // x 64 cycles after the next tile's loads, K <= 4 (profiles/r01_tune_sleep*.jsonl)
 #endif
 #ifndef HBEC_PIPE2_SLEEP
-#define HBEC_PIPE2_SLEEP 8  // pipe2 with its block barrier: 6 and 8 tie, 12 loses 4 % (r01_tune_sleep_pipe2)
+// pipe2 with its block barrier: 6 and 8 tie, 12 loses 4 % (r01_tune_sleep_pipe2);
+// with the store depth below 4 / 6 lose 4-5 / 3-4 %, 12 loses 7 % (r07_ab_pipe2_store)
+#define HBEC_PIPE2_SLEEP 8
+#endif
+#ifndef HBEC_PIPE2_STORE_DEPTH
+// pipe2 4+2: tiles whose outputs a wave keeps in registers and stores in one
+// burst (1 = each tile's outputs right after its arithmetic).  4096 x 1 MiB,
+// two allocations, against the product twice (A/A within 0.003 ms): 2 with
+// runs encode 1.081 -> 1.007-1.011 ms, reconstruct {0,1} 1.083 -> 1.004-1.007
+// (74.4 -> 80.0 % of 8 TB/s); 4 with runs 77.4 %; 2 / 4 grid-stride 77.5-78 /
+// 76.5 % (reconstruct no faster than depth 1); 8 loses 2 % either way; 65 536
+// objects 74.6 -> 79.0 % (profiles/r07_ab_pipe2_store.jsonl)
+#define HBEC_PIPE2_STORE_DEPTH 2
+#endif
+#ifndef HBEC_PIPE2_RUN
+// with a store depth T > 1: 1 = a block walks runs of 4 T consecutive tiles
+// (its burst is 4 T KiB contiguous per output), 0 = grid-stride tiles
+#define HBEC_PIPE2_RUN 1
 #endif
 #ifndef HBEC_PIPE_IMAJ
 #define HBEC_PIPE_IMAJ 0  // pipelined kernels: 1 = a shard's windows back to back (A/B)
@@ -38,8 +55,9 @@
 // tiles per launch of the aligned strided kernels (a batch splits into
 // launches of whole objects): 256 Ki tiles ran the 4096 x 1 MiB 4+2 encode
 // 72.9 -> 73.8 % and reconstruct {0,1} 70.6 -> 71.5 % against 1 Mi
-// (profiles/r05_ab_grid.jsonl, HBEC_CHUNK_TILES=262144); the other kernels
-// keep HBEC_CHUNK_TILES' 1 Mi
+// (profiles/r05_ab_grid.jsonl, HBEC_CHUNK_TILES=262144); with pipe2's store
+// depth 2: 512 Ki 80.0 -> 77.9 %, 1 Mi 74.5 % (r07_ab_pipe2_store); the other
+// kernels keep HBEC_CHUNK_TILES' 1 Mi
 #define HBEC_VEC_CHUNK_TILES 262144
 #endif
 #ifndef HBEC_PIPE_V2_MAXK

@@ -599,6 +599,18 @@ int hbec_set_force_stream(int on);
  * each launch rebuilds its objects' records (gf_odd_objrec) and offsets its
  * bases by its first object.  Process-wide; not for production use. */
 int hbec_set_odd_chunk_tiles(uint64_t tiles);
+/* Test hooks, likewise process-wide: tiles per launch (at most 2^31; 0 = the
+ * tuned default) and a cap on the grid in blocks (0 = none, negative is
+ * refused) of the aligned strided kernels, so a test drives the pipelined
+ * kernels with 1-8 blocks over several rows and launches on kilobytes of data.
+ * hbec_vec_launch_config reports the values in force. */
+int hbec_set_vec_chunk_tiles(uint64_t tiles);
+int hbec_set_vec_grid_cap(int blocks);
+int hbec_vec_launch_config(uint64_t* chunk_tiles, int* grid_cap);
+/* Store depth of the pipelined kernel gf_apply_vec_pipe2 for a k x r pass
+ * (tiles whose outputs a wave stores in one burst; 1 for every other kernel)
+ * and whether its blocks walk runs of consecutive tiles. */
+int hbec_pipe2_store_depth(int k, int r, int* depth, int* run);
 int hbec_kernel_info(int k, int r, uint64_t shard_len, int* tile_bytes, int* kind, int* blocks_per_cu);
 /* Launches since load of the odd-shard main kernels (any alignment, k <= 12
  * per pass): bitplane = the compiled XOR-network kernels of the fixed encode

@@ -45,17 +45,55 @@ VARIANTS = {
     "sleep12": (["HBEC_PIPE2_SLEEP=12"], {}),
     "u2big": (["HBEC_PIPE_U_BIG=2"], {}),
     "b2": ([], {"HBEC_BLOCKS_PER_CU": "2"}),
+    # pipe2 store schedule (profiles/r07_ab_pipe2_store.jsonl): store depth 1
+    # twice (an A/A pair: the session's noise floor), store depth T with
+    # grid-stride tiles (tN) and with block-contiguous runs (tNr)
+    "par_a": (["HBEC_PIPE2_STORE_DEPTH=1", "HBEC_PIPE2_RUN=0"], {}),
+    "par_b": (["HBEC_PIPE2_STORE_DEPTH=1", "HBEC_PIPE2_RUN=0"], {}, {}, "par_a"),
 }
+for _t in (2, 4, 8):
+    VARIANTS[f"t{_t}"] = ([f"HBEC_PIPE2_STORE_DEPTH={_t}"], {})
+    VARIANTS[f"t{_t}r"] = ([f"HBEC_PIPE2_STORE_DEPTH={_t}", "HBEC_PIPE2_RUN=1"], {})
+    # second stage, for the best arm: the pacing sleep, and tiles per launch
+    # (a third entry: test hooks called on the variant's library after loading)
+    for _r in ("", "r"):
+        _d = VARIANTS[f"t{_t}{_r}"][0]
+        for _s in (4, 6, 12):
+            VARIANTS[f"t{_t}{_r}_s{_s}"] = (_d + [f"HBEC_PIPE2_SLEEP={_s}"], {})
+        for _c in (512, 1024):
+            VARIANTS[f"t{_t}{_r}_c{_c}k"] = (_d, {}, {"hbec_set_vec_chunk_tiles": _c << 10}, f"t{_t}{_r}")
+for _c in (512, 1024):
+    VARIANTS[f"par_c{_c}k"] = (VARIANTS["par_a"][0], {}, {"hbec_set_vec_chunk_tiles": _c << 10}, "par_a")
+# Variants with a fourth entry are a copy of that variant's library (its own
+# file, so its own process-wide hook state) and are built without HBEC_TUNE,
+# as the product is: only the units that read the definitions are recompiled.
+PIPE2_UNITS = ["kernels.hip", "hbec.cpp"]
 
 
 def build(names):
+    import shutil
 
     from hummingbird_amd import build as hb
 
     for n in names:
-        defs, _ = VARIANTS[n]
+        v = VARIANTS[n]
         d = OUTDIR / n
-        hb.build(defs=["HBEC_TUNE=1"] + list(defs), lib=d / "libhbec.so", objdir=d / "obj", verbose=False)
+        if len(v) > 3:
+            if not (OUTDIR / v[3] / "libhbec.so").exists():
+                build([v[3]])
+            d.mkdir(parents=True, exist_ok=True)
+            shutil.copy2(OUTDIR / v[3] / "libhbec.so", d / "libhbec.so")
+        elif any("HBEC_PIPE2_STORE_DEPTH" in x for x in v[0]):
+            hb.build(verbose=False)
+            od = d / "obj"
+            od.mkdir(parents=True, exist_ok=True)
+            for o in hb.OBJ.glob("*.o"):
+                shutil.copy2(o, od / o.name)
+            for u in PIPE2_UNITS:
+                (od / (u.rsplit(".", 1)[0] + ".o")).unlink(missing_ok=True)
+            hb.build(verbose=False, defs=list(v[0]), lib=d / "libhbec.so", objdir=od)
+        else:
+            hb.build(defs=["HBEC_TUNE=1"] + list(v[0]), lib=d / "libhbec.so", objdir=d / "obj", verbose=False)
         print("built", n, flush=True)
 
 
@@ -72,7 +110,7 @@ def run(names, rounds, n_obj, launches, k=4, m=2, size=1 << 20):
     e = min(m, 3)  # erased data shards 0..e-1
     libs = {}
     for n in names:
-        _, env = VARIANTS[n]
+        env = VARIANTS[n][1]
         old = {var: os.environ.get(var) for var in env}
         os.environ.update(env)
         h = C.CDLL(str(OUTDIR / n / "libhbec.so"))
@@ -88,6 +126,8 @@ def run(names, rounds, n_obj, launches, k=4, m=2, size=1 << 20):
             f.restype, f.argtypes = res, args
         codec = C.c_void_p()
         assert h.hbec_new(k, m, C.byref(codec)) == 0
+        for hook, val in (VARIANTS[n][2] if len(VARIANTS[n]) > 2 else {}).items():
+            assert getattr(h, hook)(val) == 0, (n, hook)
         libs[n] = (h, codec)
 
     objs = torch.empty((n_obj, k * s), dtype=torch.uint8, device="cuda")
@@ -152,7 +192,12 @@ def run(names, rounds, n_obj, launches, k=4, m=2, size=1 << 20):
                "enc_ms_min": round(min(times[n]["enc"]), 4), "rec_ms_min": round(min(times[n]["rec"]), 4),
                "enc_GBs": round(bytes_per_launch / e_ms / 1e6, 1), "rec_GBs": round(rec_bytes / r / 1e6, 1),
                "frac": round((bytes_per_launch + rec_bytes) / (e_ms + r) / 1e6 / 8000, 4), "parity_ok": okp, "rebuilt_ok": okr,
-               "tile": tb.value, "blocks_per_cu": bpc.value}
+               "tile": tb.value, "blocks_per_cu": bpc.value, "objects": n_obj}
+        if hasattr(h, "hbec_pipe2_store_depth"):
+            dep, rn, ch = C.c_int(), C.c_int(), C.c_uint64()
+            h.hbec_pipe2_store_depth(k, m, C.byref(dep), C.byref(rn))
+            h.hbec_vec_launch_config(C.byref(ch), None)
+            row.update(store_depth=dep.value, run=rn.value, chunk_tiles=ch.value)
         res.append(row)
         print(json.dumps(row), flush=True)
     return res
