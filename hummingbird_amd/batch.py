@@ -355,6 +355,67 @@ class StripePlan:
             pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(where.data_ptr()),
             C.c_void_p(flags.data_ptr()), _stream_ptr(stream)))
 
+    def hash_mixed(self, select, digests=None, expected=None, bad=None, where=None, filter=None, filter_bits=1,
+                   stream=None):
+        """The auditor's check on this plan: the ShardHash (raw MD5) of every
+        selected shard of every examined entry, compared on the device with the
+        stored one (hbec_hash_plan_mixed).  ``select`` is an [n, k+m] array,
+        row i the shards of entry i to hash (any number set; None: every shard).
+        ``digests`` and ``expected`` are uint8 CUDA tensors of n*(k+m)*16 bytes,
+        shard j of entry i at (i*(k+m) + j)*16; at least one is needed, and
+        ``expected`` needs ``bad`` and k+m <= 32.  ``bad``, ``where`` and
+        ``filter`` are 32-bit CUDA tensors with one word per entry: bad[i] |=
+        1 << j for every hashed shard that differs from ``expected``; where[i]
+        (needs ``bad``) gets locate_mixed's word naming that shard, for
+        locate_decode and heal_mixed under ``select`` as the masks; only entries
+        with filter[i] & filter_bits are examined (None: all).  ``bad`` and
+        ``where`` are caller-zeroed and only ORed into.  A sweep that heals a
+        stripe with one surplus shard is repair_mixed, hash_mixed(present,
+        expected=..., bad=..., where=..., filter=flags), heal_mixed, queued on
+        one stream with no synchronisation."""
+        import numpy as np
+        import torch
+
+        n = self.enc.DataShards + self.enc.ParityShards
+        for name, t in (("bad", bad), ("where", where), ("filter", filter)):
+            if t is None:
+                continue
+            if t.dtype != torch.uint32 and t.dtype != torch.int32:
+                raise ValueError(f"{name} must be a 32-bit integer tensor")
+            if not t.is_cuda or not t.is_contiguous() or t.numel() < self._n:
+                raise ValueError(f"{name} must be a contiguous CUDA tensor with one entry per stripe")
+        for name, t in (("digests", digests), ("expected", expected)):
+            if t is None:
+                continue
+            if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.numel() < self._n * n * 16:
+                raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor of n * (k+m) * 16 bytes")
+        p = np.ones((self._n, n), bool) if select is None else np.asarray(select) != 0
+        if p.ndim != 2 or p.shape[0] != self._n or p.shape[1] != n:
+            raise ValueError("select must be [n_stripes, k+m]")
+        if self._n == 0:
+            rows, row_of = p.astype(np.uint8), np.zeros(0, np.uint32)
+        else:
+            rows, row_of = np.unique(p.astype(np.uint8), axis=0, return_inverse=True)
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        row_of = np.ascontiguousarray(row_of.reshape(-1), dtype=np.uint32)
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+
+        check(N.lib().hbec_hash_plan_mixed(
+            self.enc.handle, self._h, rows.ctypes.data_as(N._U8P), rows.shape[0],
+            row_of.ctypes.data_as(C.POINTER(C.c_uint32)), ptr(filter), int(filter_bits) & 0xFFFFFFFF,
+            ptr(expected), ptr(digests), ptr(bad), ptr(where), _stream_ptr(stream)))
+
+
+def hash_plan_stats():
+    """Since load, for StripePlan.hash_mixed: launches of its kernels, md5_plan
+    and (with ``where``) hash_where (`kernel_launches`), and chains listed, one
+    per selected shard of a non-empty entry (`chains`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_hash_plan_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "chains": b.value}
+
 
 def locate_decode(k: int, m: int, present, where_array):
     """The shard every word of ``where_array`` names (hbec_locate_decode; host

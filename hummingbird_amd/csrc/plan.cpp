@@ -14,6 +14,9 @@
 // list (vmixed.h, vmixed.hip), and so does the call that rebuilds and checks in
 // one pass (hbec_repair_plan_mixed; repair.h, repair.hip) and the call that
 // rebuilds the shard locate named (hbec_heal_plan_mixed; heal.h, heal.hip).
+// The ShardHash audit of a plan (hbec_hash_plan_mixed; hashplan.h, hashplan.hip)
+// has records of its own with 64-bit lengths, built on first use likewise, and
+// stages its chain list where those calls stage their words.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +29,7 @@
 
 #include "../../include/hbec.h"
 #include "gf256.h"
+#include "hashplan.h"
 #include "heal.h"
 #include "internal.h"
 #include "kernels.h"
@@ -105,6 +109,11 @@ struct hbec_plan {
     mutable uint32_t* d_heal = nullptr;
     mutable size_t heal_dev_words = 0;
     mutable std::shared_ptr<const hbec::HealStage> heal_on_device;  // what d_heal holds
+    // hbec_hash_plan_mixed: a record per source entry with its length in 64 bits
+    // and the non-empty entries longest first, built by the first such call (mp_mu)
+    mutable bool hash_built = false;
+    mutable hbec::HRec* d_hrecs = nullptr;
+    mutable std::vector<uint32_t> hash_order;
 };
 
 // The gf_odd_rec records of a plan pass depend only on the plan's stripes and
@@ -1227,6 +1236,88 @@ int heal_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* pat
     return HBEC_OK;
 }
 
+// ---- the ShardHash of a plan's shards against the stored ones (hbec_hash_plan_mixed) ----
+
+std::atomic<uint64_t> g_hashplan_launches{0}, g_hashplan_chains{0};
+
+// The device side of a plan's hash call, built once: a record per source entry
+// and the order its chains are listed in.
+int hash_plan_device(const hbec_plan* p) {
+    std::lock_guard<std::mutex> lk(p->mp_mu);
+    if (p->hash_built) return HBEC_OK;
+    std::vector<hbec::HRec> recs(p->src.size());
+    for (size_t i = 0; i < p->src.size(); ++i) {
+        const hbec::MSrc& s = p->src[i];
+        recs[i] = hbec::HRec{s.a, s.b, s.shard_len, (uint32_t)hbec::loc_route(p->k, p->m, s.shard_len), 0u};
+    }
+    int rc = upload(recs, &p->d_hrecs, "plan hash records");
+    if (rc) return rc;
+    hbec::hash_order(p->src, p->hash_order);
+    p->hash_built = true;
+    return HBEC_OK;
+}
+
+int hash_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* select, uint32_t n_select,
+                    const uint32_t* select_of, const uint32_t* d_filter, uint32_t filter_bits,
+                    const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad, uint32_t* d_where,
+                    hipStream_t stream) {
+    if (!codec || !plan) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
+    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
+    if (n_select > 65536) return fail(HBEC_ERR_INVALID_ARG, "more than 65536 selection rows");
+    // what the given pointers say about each other holds for any plan
+    if (d_where && !d_bad) return fail(HBEC_ERR_INVALID_ARG, "d_where needs d_bad");
+    if (d_expected && !d_bad) return fail(HBEC_ERR_INVALID_ARG, "d_expected needs d_bad");
+    if (d_expected && n > 32) return fail(HBEC_ERR_INVALID_ARG, "d_expected needs k + m <= 32 (one bit per shard)");
+    if ((d_bad && (d_bad == d_where || d_bad == d_filter)) || (d_where && d_where == d_filter))
+        return fail(HBEC_ERR_INVALID_ARG, "d_bad, d_where and d_filter must be distinct");
+    if ((reinterpret_cast<uintptr_t>(d_digests) | reinterpret_cast<uintptr_t>(d_expected)) & 3u)
+        return fail(HBEC_ERR_INVALID_ARG, "digest buffer not 4-byte aligned");
+    const uint64_t n_src = plan->n_src;
+    if (n_src == 0) return HBEC_OK;
+    if (!select || !select_of) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    if (!n_select) return fail(HBEC_ERR_INVALID_ARG, "stripes but no selection rows");
+    if (!d_digests && !d_expected) return fail(HBEC_ERR_INVALID_ARG, "neither d_digests nor d_expected given");
+    bool any = false;
+    for (uint64_t i = 0; i < n_src; ++i) {  // zero-length entries too
+        if (select_of[i] >= n_select)
+            return fail(HBEC_ERR_INVALID_ARG, "selection index out of range (stripe " + std::to_string(i) + ")");
+        any = any || plan->src[i].shard_len;
+    }
+    if (!any) return HBEC_OK;  // zero-length entries only
+    int rc = hash_plan_device(plan);
+    if (rc) return rc;
+    // per call: the chain list, then (for d_where) every entry's selected-shard bits
+    std::vector<hbec::HChain> chains;
+    hbec::hash_chains(plan->hash_order, n, select, n_select, select_of, chains);
+    if (chains.empty()) return HBEC_OK;
+    if (chains.size() / 64 >= (1ull << 31)) return fail(HBEC_ERR_INVALID_ARG, "call too large (>= 2^37 chains)");
+    const size_t chain_words = chains.size() * (sizeof(hbec::HChain) / 4);
+    std::vector<uint32_t> stage(chain_words + (d_where ? (size_t)n_src : 0));
+    std::memcpy(stage.data(), chains.data(), chain_words * 4);
+    if (d_where) {
+        std::vector<uint32_t> bits(n_select);
+        for (uint32_t p = 0; p < n_select; ++p) bits[p] = hbec::hash_select_bits(n, select + (size_t)p * n);
+        for (uint64_t i = 0; i < n_src; ++i) stage[chain_words + i] = bits[select_of[i]];
+    }
+    std::lock_guard<std::mutex> lk(plan->mp_mu);
+    rc = stage_begin(plan, stage, stream);
+    if (rc) return rc;
+    const hbec::HChain* d_chains = reinterpret_cast<const hbec::HChain*>(plan->d_mstage);
+    g_hashplan_launches.fetch_add(1, std::memory_order_relaxed);
+    g_hashplan_chains.fetch_add(chains.size(), std::memory_order_relaxed);
+    hipError_t e = hbec::launch_md5_plan(plan->d_hrecs, d_chains, chains.size(), k, n, d_filter, filter_bits,
+                                         d_expected, d_digests, d_expected ? d_bad : nullptr, stream);
+    if (e == hipSuccess && d_where) {
+        g_hashplan_launches.fetch_add(1, std::memory_order_relaxed);
+        e = hbec::launch_hash_where(plan->d_hrecs, (uint32_t)n_src, plan->d_mstage + chain_words, d_filter,
+                                    filter_bits, d_bad, d_where, stream);
+    }
+    rc = stage_end(plan, stream);
+    if (e != hipSuccess) return hip_fail(e, "launch md5_plan");
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1424,6 +1515,7 @@ void hbec_plan_free(hbec_plan* plan) {
     if (plan->d_mtiles) (void)hipFree(plan->d_mtiles);
     if (plan->d_mstage) (void)hipFree(plan->d_mstage);
     if (plan->d_heal) (void)hipFree(plan->d_heal);
+    if (plan->d_hrecs) (void)hipFree(plan->d_hrecs);
     if (plan->mp_ev) (void)hipEventDestroy(plan->mp_ev);
     for (uint32_t* l : plan->d_lists)
         if (l) (void)hipFree(l);
@@ -1622,6 +1714,25 @@ int hbec_heal_plan_tile_bytes(void) { return (int)hbec::heal_plan_tile_bytes(); 
 int hbec_set_heal_plan_chunk_tiles(uint64_t tiles) {
     return hbec::guarded("hbec_set_heal_plan_chunk_tiles", [&]() -> int {
         g_healplan_chunk_override.store(tiles, std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_hash_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* select, uint32_t n_select,
+                         const uint32_t* select_of, const uint32_t* d_filter, uint32_t filter_bits,
+                         const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad, uint32_t* d_where,
+                         void* hip_stream) {
+    return hbec::guarded("hbec_hash_plan_mixed", [&]() -> int {
+        return hash_plan_mixed(codec, plan, select, n_select, select_of, d_filter, filter_bits, d_expected, d_digests,
+                               d_bad, d_where, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_hash_plan_stats(uint64_t* kernel_launches, uint64_t* chains) {
+    return hbec::guarded("hbec_hash_plan_stats", [&]() -> int {
+        if (!kernel_launches || !chains) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *kernel_launches = g_hashplan_launches.load(std::memory_order_relaxed);
+        *chains = g_hashplan_chains.load(std::memory_order_relaxed);
         return HBEC_OK;
     });
 }

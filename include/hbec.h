@@ -508,6 +508,57 @@ int hbec_heal_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries);
 int hbec_heal_plan_tile_bytes(void);
 /* test hook, as hbec_set_verify_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
 int hbec_set_heal_plan_chunk_tiles(uint64_t tiles);
+/* The auditor's check on a plan (objectserver/auditor.go:100-156): the ShardHash, the raw MD5
+ * of the shard body (indexdb.go:746-753), of selected shards, compared on the device with the
+ * stored ones, and the result in the form hbec_heal_plan_mixed reads.  A shard whose hash
+ * differs is the corrupt one whatever the number of surplus shards, so the sweep
+ * hbec_repair_plan_mixed, this call with d_filter = its flags, hbec_heal_plan_mixed heals a
+ * stripe with ONE surplus shard, where hbec_locate_plan_mixed can only say HBEC_LOC_BAD.
+ * select / n_select / select_of: host arrays with the layout of patterns / n_patterns /
+ * pattern_of of hbec_verify_plan_mixed (n_select rows of k + m bytes, non-zero = shard
+ * selected; one row index per source entry, zero-length entries included), copied before the
+ * call returns.  A row only selects shards: any number of bytes may be set, none included, and
+ * there is no HBEC_ERR_TOO_FEW_SHARDS.
+ * Entry i is examined when d_filter is NULL or d_filter[i] & filter_bits (uint32, device, one
+ * word per source entry; read on the device, nothing is copied back).  A chain is one selected
+ * shard of one examined, non-empty entry; shard j of an entry lies where the plan's other
+ * calls put it, its length is 64-bit, and every (k, m) the plan accepts is hashed.
+ * d_digests (may be NULL): the raw MD5 of chain (i, j) goes to d_digests + (i (k + m) + j) 16,
+ * hbec_encode_md5_batch's layout; device, 4-byte aligned; no other byte of it is written.
+ * d_expected (may be NULL): the stored digests in the same layout, read only for chains; it
+ * needs d_bad and k + m <= 32.  d_bad (may be NULL without d_expected): uint32, device, one
+ * word per source entry, caller-zeroed, only ever ORed into: d_bad[i] |= 1u << j when the
+ * digest of chain (i, j) differs from the expected one.
+ * d_where (may be NULL; needs d_bad): uint32, device, one word per source entry, caller-zeroed,
+ * ORed into, in hbec_locate_plan_mixed's format, so hbec_locate_decode and
+ * hbec_heal_plan_mixed take the words as they are.  For an examined, non-empty entry of
+ * k <= 12, m <= 4 and shards below 2^31 - 64 KiB, with sel its selected-shard bits:
+ *   d_bad[i] == 0            nothing
+ *   exactly one bit j        HBEC_LOC_BAD | (sel & ~(1u << j) & 0xFFFF): names shard j
+ *   two or more bits         HBEC_LOC_BAD | (sel & 0xFFFF): HBEC_LOC_MULTIPLE; d_bad says which
+ * Every other non-empty entry gets HBEC_LOC_SKIPPED, filtered or not, as locate gives it; its
+ * digests and d_bad are computed all the same.  A word names a shard only under the mask that
+ * was the selection: pass hbec_locate_decode and hbec_heal_plan_mixed the same masks.
+ * Errors, all HBEC_ERR_INVALID_ARG and all found before anything is queued or written: a null
+ * codec or plan; a plan built for another (k, m); n_select > 65536; d_where or d_expected
+ * without d_bad; d_expected with k + m > 32; d_bad, d_where and d_filter not pairwise
+ * distinct; a digest buffer that is not 4-byte aligned; and for a plan with entries a null
+ * select or select_of, n_select == 0, an index >= n_select, neither d_digests nor d_expected.
+ * A plan with no entries accepts null device pointers and launches nothing; so does a call
+ * with no chain on the host side (every selection row empty, or zero-length entries only).
+ * One lane hashes one chain and MD5 is serial within a shard, so a call lasts at least as long
+ * as its longest examined chain, however few are examined.  One digest per (entry, shard) is
+ * the ShardHash of a one-stripe object; the hash of a multi-stripe shard file is a chain across
+ * entries and stays with hbec_md5_new / hbec_md5_update / hbec_md5_final.
+ * Queued on hip_stream and not waited for; calls on one plan take turns with the other
+ * hbec_*_plan_mixed calls. */
+int hbec_hash_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* select, uint32_t n_select,
+                         const uint32_t* select_of, const uint32_t* d_filter, uint32_t filter_bits,
+                         const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad, uint32_t* d_where,
+                         void* hip_stream);
+/* since load: launches of the hash call's kernels (md5_plan, and hash_where when d_where is
+ * given), and chains listed */
+int hbec_hash_plan_stats(uint64_t* kernel_launches, uint64_t* chains);
 
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
