@@ -408,6 +408,77 @@ class StripePlan:
             ptr(expected), ptr(digests), ptr(bad), ptr(where), _stream_ptr(stream)))
 
 
+    def hash_files(self, object_start, select=None, digests=None, expected=None, bad=None, where=None, filter=None,
+                   filter_bits=1, stream=None):
+        """hash_mixed for objects of more than one stripe: the ShardHash of a
+        shard FILE, shard j of each of the object's entries back to back, as
+        ecSplit writes it (hbec_hash_plan_files).  ``object_start`` has
+        n_objects + 1 entries: object g is the plan's entries
+        [object_start[g], object_start[g+1]); it starts at 0, never decreases
+        and ends at the plan's entry count.  ``select`` is [n_objects, k+m]
+        (None: every shard file).  ``digests`` and ``expected`` hold
+        n_objects*(k+m)*16 bytes, file j of object g at (g*(k+m) + j)*16, and
+        ``bad`` one word per object.  ``where`` and ``filter`` have one word
+        per ENTRY: an object is hashed when any of its entries passes the
+        filter, and each passing entry gets the word heal_mixed reads.  The
+        sweep is repair_mixed(present, flags), hash_files(object_start,
+        select, expected=..., bad=..., where=..., filter=flags),
+        heal_mixed(present, where, healed) on one stream, ``present`` being the
+        object's row of ``select`` repeated for its entries.  Everything else
+        as in hash_mixed, which is the quicker call for one-stripe objects."""
+        import numpy as np
+        import torch
+
+        n = self.enc.DataShards + self.enc.ParityShards
+        starts = np.asarray(object_start)
+        if starts.ndim != 1 or starts.size < 1 or starts.dtype.kind not in "iu":
+            raise ValueError("object_start must be a 1-D integer array of n_objects + 1 entries")
+        if starts.size and (starts.min() < 0 or starts.max() > 0xFFFFFFFF):
+            raise ValueError("object_start must hold entry indices")
+        starts = np.ascontiguousarray(starts, dtype=np.uint32)
+        n_obj = starts.size - 1
+        for name, t, need, per in (("bad", bad, n_obj, "object"), ("where", where, self._n, "stripe"),
+                                   ("filter", filter, self._n, "stripe")):
+            if t is None:
+                continue
+            if t.dtype != torch.uint32 and t.dtype != torch.int32:
+                raise ValueError(f"{name} must be a 32-bit integer tensor")
+            if not t.is_cuda or not t.is_contiguous() or t.numel() < need:
+                raise ValueError(f"{name} must be a contiguous CUDA tensor with one entry per {per}")
+        for name, t in (("digests", digests), ("expected", expected)):
+            if t is None:
+                continue
+            if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.numel() < n_obj * n * 16:
+                raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor of n_objects * (k+m) * 16 bytes")
+        p = np.ones((n_obj, n), bool) if select is None else np.asarray(select) != 0
+        if p.ndim != 2 or p.shape[0] != n_obj or p.shape[1] != n:
+            raise ValueError("select must be [n_objects, k+m]")
+        if n_obj == 0:
+            rows, row_of = p.astype(np.uint8), np.zeros(0, np.uint32)
+        else:
+            rows, row_of = np.unique(p.astype(np.uint8), axis=0, return_inverse=True)
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        row_of = np.ascontiguousarray(row_of.reshape(-1), dtype=np.uint32)
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+
+        check(N.lib().hbec_hash_plan_files(
+            self.enc.handle, self._h, starts.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
+            rows.ctypes.data_as(N._U8P), rows.shape[0], row_of.ctypes.data_as(C.POINTER(C.c_uint32)), ptr(filter),
+            int(filter_bits) & 0xFFFFFFFF, ptr(expected), ptr(digests), ptr(bad), ptr(where), _stream_ptr(stream)))
+
+
+def hash_files_stats():
+    """Since load, for StripePlan.hash_files: launches of its kernels, md5_files
+    and (with ``where``) hash_files_where (`kernel_launches`), chains listed,
+    one per selected shard file of an object with a byte in it (`chains`), and
+    the non-empty entries those chains walk, once per chain (`segments`)."""
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_hash_files_stats(C.byref(a), C.byref(b), C.byref(c)))
+    return {"kernel_launches": a.value, "chains": b.value, "segments": c.value}
+
+
 def hash_plan_stats():
     """Since load, for StripePlan.hash_mixed: launches of its kernels, md5_plan
     and (with ``where``) hash_where (`kernel_launches`), and chains listed, one

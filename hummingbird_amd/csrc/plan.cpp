@@ -16,7 +16,9 @@
 // rebuilds the shard locate named (hbec_heal_plan_mixed; heal.h, heal.hip).
 // The ShardHash audit of a plan (hbec_hash_plan_mixed; hashplan.h, hashplan.hip)
 // has records of its own with 64-bit lengths, built on first use likewise, and
-// stages its chain list where those calls stage their words.
+// stages its chain list where those calls stage their words.  The hash of
+// multi-stripe shard files (hbec_hash_plan_files; hashfiles.h, hashfiles.hip)
+// reads the same records and stages its chains and object table there too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +31,7 @@
 
 #include "../../include/hbec.h"
 #include "gf256.h"
+#include "hashfiles.h"
 #include "hashplan.h"
 #include "heal.h"
 #include "internal.h"
@@ -1318,6 +1321,77 @@ int hash_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* sel
     return rc;
 }
 
+// ---- the ShardHash of multi-stripe shard files on a plan (hbec_hash_plan_files) ----
+
+std::atomic<uint64_t> g_hashfiles_launches{0}, g_hashfiles_chains{0}, g_hashfiles_segments{0};
+
+int hash_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                    const uint8_t* select, uint32_t n_select, const uint32_t* select_of, const uint32_t* d_filter,
+                    uint32_t filter_bits, const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad,
+                    uint32_t* d_where, hipStream_t stream) {
+    if (!codec || !plan) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
+    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
+    if (n_select > 65536) return fail(HBEC_ERR_INVALID_ARG, "more than 65536 selection rows");
+    // what the given pointers say about each other holds for any plan, as in hash_plan_mixed
+    if (d_where && !d_bad) return fail(HBEC_ERR_INVALID_ARG, "d_where needs d_bad");
+    if (d_expected && !d_bad) return fail(HBEC_ERR_INVALID_ARG, "d_expected needs d_bad");
+    if (d_expected && n > 32) return fail(HBEC_ERR_INVALID_ARG, "d_expected needs k + m <= 32 (one bit per shard)");
+    if ((d_bad && (d_bad == d_where || d_bad == d_filter)) || (d_where && d_where == d_filter))
+        return fail(HBEC_ERR_INVALID_ARG, "d_bad, d_where and d_filter must be distinct");
+    if ((reinterpret_cast<uintptr_t>(d_digests) | reinterpret_cast<uintptr_t>(d_expected)) & 3u)
+        return fail(HBEC_ERR_INVALID_ARG, "digest buffer not 4-byte aligned");
+    const uint64_t n_src = plan->n_src;
+    if (n_src == 0) return HBEC_OK;
+    if (const char* why = hbec::files_check_objects(object_start, n_objects, n_src))
+        return fail(HBEC_ERR_INVALID_ARG, why);
+    if (!select || !select_of) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    if (!d_digests && !d_expected) return fail(HBEC_ERR_INVALID_ARG, "neither d_digests nor d_expected given");
+    for (uint32_t g = 0; g < n_objects; ++g)  // empty objects too
+        if (select_of[g] >= n_select)
+            return fail(HBEC_ERR_INVALID_ARG, "selection index out of range (object " + std::to_string(g) + ")");
+    // per call: the chain list and the object table, then (for d_where) every entry's object
+    // and every object's selected-shard bits
+    std::vector<hbec::FChain> chains;
+    const uint64_t segments = hbec::files_chains(plan->src, object_start, n_objects, n, select, n_select, select_of,
+                                                 chains);
+    if (chains.empty()) return HBEC_OK;  // zero-length entries only, or nothing selected
+    if (chains.size() / 64 >= (1ull << 31)) return fail(HBEC_ERR_INVALID_ARG, "call too large (>= 2^37 chains)");
+    int rc = hash_plan_device(plan);
+    if (rc) return rc;
+    const size_t chain_words = chains.size() * (sizeof(hbec::FChain) / 4);
+    const size_t objects_at = chain_words, of_at = objects_at + n_objects + 1, sel_at = of_at + (size_t)n_src;
+    std::vector<uint32_t> stage(d_where ? sel_at + n_objects : of_at);
+    std::memcpy(stage.data(), chains.data(), chain_words * 4);
+    std::memcpy(stage.data() + objects_at, object_start, ((size_t)n_objects + 1) * 4);
+    if (d_where) {
+        std::vector<uint32_t> object_of;
+        hbec::files_entry_objects(object_start, n_objects, object_of);
+        std::memcpy(stage.data() + of_at, object_of.data(), (size_t)n_src * 4);
+        for (uint32_t g = 0; g < n_objects; ++g)
+            stage[sel_at + g] = hbec::hash_select_bits(n, select + (size_t)select_of[g] * n);
+    }
+    std::lock_guard<std::mutex> lk(plan->mp_mu);
+    rc = stage_begin(plan, stage, stream);
+    if (rc) return rc;
+    const uint32_t* d_stage = plan->d_mstage;
+    g_hashfiles_launches.fetch_add(1, std::memory_order_relaxed);
+    g_hashfiles_chains.fetch_add(chains.size(), std::memory_order_relaxed);
+    g_hashfiles_segments.fetch_add(segments, std::memory_order_relaxed);
+    hipError_t e = hbec::launch_md5_files(plan->d_hrecs, d_stage + objects_at,
+                                          reinterpret_cast<const hbec::FChain*>(d_stage), chains.size(), k, n,
+                                          d_filter, filter_bits, d_expected, d_digests,
+                                          d_expected ? d_bad : nullptr, stream);
+    if (e == hipSuccess && d_where) {
+        g_hashfiles_launches.fetch_add(1, std::memory_order_relaxed);
+        e = hbec::launch_hash_files_where(plan->d_hrecs, (uint32_t)n_src, d_stage + of_at, d_stage + sel_at, d_filter,
+                                          filter_bits, d_bad, d_where, stream);
+    }
+    rc = stage_end(plan, stream);
+    if (e != hipSuccess) return hip_fail(e, "launch md5_files");
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1733,6 +1807,27 @@ int hbec_hash_plan_stats(uint64_t* kernel_launches, uint64_t* chains) {
         if (!kernel_launches || !chains) return fail(HBEC_ERR_INVALID_ARG, "null argument");
         *kernel_launches = g_hashplan_launches.load(std::memory_order_relaxed);
         *chains = g_hashplan_chains.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_hash_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                         const uint8_t* select, uint32_t n_select, const uint32_t* select_of,
+                         const uint32_t* d_filter, uint32_t filter_bits, const uint8_t* d_expected,
+                         uint8_t* d_digests, uint32_t* d_bad, uint32_t* d_where, void* hip_stream) {
+    return hbec::guarded("hbec_hash_plan_files", [&]() -> int {
+        return hash_plan_files(codec, plan, object_start, n_objects, select, n_select, select_of, d_filter,
+                               filter_bits, d_expected, d_digests, d_bad, d_where,
+                               static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_hash_files_stats(uint64_t* kernel_launches, uint64_t* chains, uint64_t* segments) {
+    return hbec::guarded("hbec_hash_files_stats", [&]() -> int {
+        if (!kernel_launches || !chains || !segments) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *kernel_launches = g_hashfiles_launches.load(std::memory_order_relaxed);
+        *chains = g_hashfiles_chains.load(std::memory_order_relaxed);
+        *segments = g_hashfiles_segments.load(std::memory_order_relaxed);
         return HBEC_OK;
     });
 }

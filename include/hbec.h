@@ -549,7 +549,7 @@ int hbec_set_heal_plan_chunk_tiles(uint64_t tiles);
  * One lane hashes one chain and MD5 is serial within a shard, so a call lasts at least as long
  * as its longest examined chain, however few are examined.  One digest per (entry, shard) is
  * the ShardHash of a one-stripe object; the hash of a multi-stripe shard file is a chain across
- * entries and stays with hbec_md5_new / hbec_md5_update / hbec_md5_final.
+ * entries: hbec_hash_plan_files below computes and compares it on the same plan.
  * Queued on hip_stream and not waited for; calls on one plan take turns with the other
  * hbec_*_plan_mixed calls. */
 int hbec_hash_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* select, uint32_t n_select,
@@ -559,6 +559,49 @@ int hbec_hash_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t
 /* since load: launches of the hash call's kernels (md5_plan, and hash_where when d_where is
  * given), and chains listed */
 int hbec_hash_plan_stats(uint64_t* kernel_launches, uint64_t* chains);
+/* hbec_hash_plan_mixed for objects of more than one stripe.  The reference's ShardHash is the
+ * MD5 of the whole shard FILE, and ecSplit appends shard j of every stripe to writer j
+ * (ecutils.go:38-70): the file is shard j of each of the object's stripes back to back, each
+ * piece chunk_size bytes (ecengine.go:725-726) and the last one shorter.
+ * object_start (host, n_objects + 1 words, copied before the call returns): object g is the
+ * plan's source entries [object_start[g], object_start[g + 1]), in stripe order; it starts at
+ * 0, never decreases and ends at the plan's entry count.  Chain (g, j) is shard j of each of
+ * those entries in order, every piece where the plan's other calls put it (a + j len for data
+ * shards, b + (j - k) len for parity), hashed as ONE stream: the total length is 64-bit and the
+ * MD5 pad and bit length are taken over it.  An object with no entries, or with zero-length
+ * entries only, has no chain and its slots are left untouched.
+ * select / n_select / select_of: as in hbec_hash_plan_mixed, but one row index per OBJECT.
+ * Object g is examined when d_filter is NULL or ANY of its entries has d_filter[i] &
+ * filter_bits (one word per ENTRY, device): a shard file can only be hashed whole.
+ * d_digests / d_expected: as in hbec_hash_plan_mixed with the object for the entry: chain
+ * (g, j) at (g (k + m) + j) 16.  d_bad: one word per OBJECT, caller-zeroed, d_bad[g] |= 1u << j
+ * where the digest of chain (g, j) differs from the expected one.
+ * d_where (needs d_bad): one word per ENTRY, caller-zeroed, ORed into, so
+ * hbec_heal_plan_mixed takes it unchanged.  A non-empty entry i of object g with k <= 12,
+ * m <= 4 and shards below 2^31 - 64 KiB that itself passes the filter (NULL: every entry) gets
+ * the word hbec_hash_plan_mixed would give an entry with g's selection and d_bad[g]; every
+ * other non-empty entry gets HBEC_LOC_SKIPPED, filtered or not.  The sweep is
+ * hbec_repair_plan_mixed (present, flags), this call with d_filter = flags, then
+ * hbec_heal_plan_mixed (present, d_where, healed), queued on one stream with no host trip;
+ * present is the object's row repeated for its entries, since a lost shard file is lost in
+ * every stripe.  A word names a shard only under that mask: pass hbec_locate_decode and
+ * hbec_heal_plan_mixed the masks that were the selection.
+ * Errors, all HBEC_ERR_INVALID_ARG and all found before anything is queued or written: those
+ * of hbec_hash_plan_mixed that concern the codec, the plan, n_select and the device pointers;
+ * and for a plan with entries a null object_start, n_objects == 0, object_start[0] != 0, a
+ * decreasing pair, a last word other than the entry count, a null select or select_of, an
+ * index >= n_select, neither d_digests nor d_expected.  A plan with no entries accepts nulls
+ * and launches nothing.
+ * One lane hashes one chain, so a call lasts as long as its longest examined file.  For
+ * one-stripe objects hbec_hash_plan_mixed computes the same and is the quicker call.
+ * Queued on hip_stream and not waited for, as hbec_hash_plan_mixed. */
+int hbec_hash_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                         const uint8_t* select, uint32_t n_select, const uint32_t* select_of,
+                         const uint32_t* d_filter, uint32_t filter_bits, const uint8_t* d_expected,
+                         uint8_t* d_digests, uint32_t* d_bad, uint32_t* d_where, void* hip_stream);
+/* since load: launches of that call's kernels (md5_files, and hash_files_where when d_where is
+ * given), chains listed, and segments those chains walk (non-empty entries, once per chain) */
+int hbec_hash_files_stats(uint64_t* kernel_launches, uint64_t* chains, uint64_t* segments);
 
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
