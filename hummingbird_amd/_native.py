@@ -100,6 +100,7 @@ _SIG = [
     ("hbec_md5_update", C.c_int, [_P, C.POINTER(View), C.c_uint64, _P]),
     ("hbec_md5_final", C.c_int, [_P, _P, _P]),
     ("hbec_encode_md5_batch", C.c_int, [_P, C.POINTER(View), C.c_uint64, C.c_uint64, _P, _P]),
+    ("hbec_md5_route_stats", C.c_int, [C.POINTER(C.c_uint64)] * 4),
     ("hbec_decode_rows", C.c_int,
      [_P, _U8P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _U8P]),
     ("hbec_apply_batch", C.c_int,

@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "gf_device.h"
 #include "kernels.h"
 #include "md5_device.h"
@@ -269,11 +271,15 @@ __global__ __launch_bounds__(64) void md5_list(const Md5ListRec* __restrict__ re
 
 uint64_t md5_state_bytes() { return sizeof(Md5State); }
 
+// launches since load: md5_chains<true>, md5_chains<false>, md5_list<true>, md5_list<false> (hbec_md5_route_stats)
+std::atomic<uint64_t> g_md5_launches[4];
+
 // recs: device array of n records ({addr, len, slot, 0}); aligned = every addr 16-B aligned.
 hipError_t launch_md5_list(const void* recs, uint64_t n, uint8_t* digest, bool aligned, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const dim3 grid((unsigned)((n + 63) / 64));
     const Md5ListRec* r = static_cast<const Md5ListRec*>(recs);
+    g_md5_launches[aligned ? 2 : 3].fetch_add(1, std::memory_order_relaxed);
     if (aligned)
         hipLaunchKernelGGL(md5_list<true>, grid, dim3(64), 0, stream, r, n, digest);
     else
@@ -301,6 +307,7 @@ hipError_t launch_md5(const void* const* bases, const uint64_t* strides, int n_v
     a.view0 = view0;
     a.flags = flags;
     const dim3 grid((unsigned)((n_obj + HBEC_MD5_BLOCK - 1) / HBEC_MD5_BLOCK), (unsigned)n_views);
+    g_md5_launches[aligned ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
     if (aligned)
         hipLaunchKernelGGL((md5_chains<true, HBEC_MD5_DEPTH>), grid, dim3(HBEC_MD5_BLOCK), 0, stream, a);
     else
@@ -309,3 +316,12 @@ hipError_t launch_md5(const void* const* bases, const uint64_t* strides, int n_v
 }
 
 }  // namespace hbec
+
+extern "C" int hbec_md5_route_stats(uint64_t* chains_aligned, uint64_t* chains_unaligned, uint64_t* list_aligned,
+                                    uint64_t* list_unaligned) {
+    if (chains_aligned) *chains_aligned = hbec::g_md5_launches[0].load();
+    if (chains_unaligned) *chains_unaligned = hbec::g_md5_launches[1].load();
+    if (list_aligned) *list_aligned = hbec::g_md5_launches[2].load();
+    if (list_unaligned) *list_unaligned = hbec::g_md5_launches[3].load();
+    return 0;
+}

@@ -116,6 +116,14 @@ class MD5Chains:
         return digests
 
 
+def md5_route_stats():
+    """Launches since load of the MD5 kernels (hbec_md5_route_stats): md5_chains
+    with 16-B loads and bytewise, md5_list likewise."""
+    v = [C.c_uint64() for _ in range(4)]
+    check(N.lib().hbec_md5_route_stats(*[C.byref(x) for x in v]))
+    return dict(zip(("chains_aligned", "chains_unaligned", "list_aligned", "list_unaligned"), (x.value for x in v)))
+
+
 def hexdigests(digests):
     """uint8 [..., 16] digests -> nested lists of hex strings (ShardHash form)."""
     import numpy as np

@@ -238,6 +238,16 @@ int hbec_md5_final(hbec_md5* ctx, uint8_t* d_digests, void* hip_stream);
 int hbec_encode_md5_batch(hbec_codec* codec, const hbec_view* views, uint64_t n_objects, uint64_t shard_len,
                           uint8_t* d_digests, void* hip_stream);
 
+/* Launches since load of the kernels behind every call above and behind the
+ * host-path hashes: md5_chains (one-shot batches, streaming steps, the
+ * encode+hash segments; at most 32 views per launch) with 16-B loads when the
+ * first whole block of every view is 16-B aligned (base + 64 - carried bytes
+ * and the object stride) and bytewise otherwise, and md5_list (device lists,
+ * host chunks, the host path's arenas) likewise by its addresses.  Any pointer
+ * may be NULL. */
+int hbec_md5_route_stats(uint64_t* chains_aligned, uint64_t* chains_unaligned, uint64_t* list_aligned,
+                         uint64_t* list_unaligned);
+
 /* The decode rows a reconstruct applies: survivors[0..k) (shard indices read),
  * outputs[0..*n_outputs) (shard indices written), rows[*n_outputs][k]. */
 int hbec_decode_rows(hbec_codec* codec, const uint8_t* present, int data_only, int* survivors, int* outputs,
