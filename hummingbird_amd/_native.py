@@ -168,6 +168,7 @@ _SIG = [
     ("hbec_set_vec_chunk_tiles", C.c_int, [C.c_uint64]),
     ("hbec_set_vec_grid_cap", C.c_int, [C.c_int]),
     ("hbec_vec_launch_config", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    ("hbec_vec_kernel_stats", C.c_int, [C.POINTER(C.c_uint64)] * 5),
     ("hbec_pipe2_store_depth", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("hbec_kernel_info", C.c_int,
      [C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -672,12 +672,12 @@ def set_odd_chunk_tiles(tiles: int) -> None:
 
 
 def set_vec_chunk_tiles(tiles: int) -> None:
-    """Test hook: aligned strided launches of at most `tiles` tiles (0 = default)."""
+    """Test hook: aligned strided launches, packed ones included, of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_vec_chunk_tiles(int(tiles)))
 
 
 def set_vec_grid_cap(blocks: int) -> None:
-    """Test hook: at most `blocks` blocks per aligned strided launch (0 = no cap)."""
+    """Test hook: at most `blocks` blocks per aligned strided launch, packed ones included (0 = no cap)."""
     check(N.lib().hbec_set_vec_grid_cap(int(blocks)))
 
 
@@ -686,6 +686,14 @@ def vec_launch_config() -> tuple[int, int]:
     t, g = C.c_uint64(), C.c_int()
     check(N.lib().hbec_vec_launch_config(C.byref(t), C.byref(g)))
     return t.value, g.value
+
+
+def vec_kernel_stats():
+    """Launches since load of the aligned strided apply kernels, by the kernel
+    launched (hbec_vec_kernel_stats): packed, pipe2, pipe, vec, stream."""
+    v = [C.c_uint64() for _ in range(5)]
+    check(N.lib().hbec_vec_kernel_stats(*[C.byref(x) for x in v]))
+    return dict(zip(("packed", "pipe2", "pipe", "vec", "stream"), (x.value for x in v)))
 
 
 def pipe2_store_depth(k: int, r: int) -> tuple[int, bool]:

@@ -103,13 +103,19 @@ static const uint64_t g_vec_chunk_tiles = [] {
     return (uint64_t)(v > 0 ? v : HBEC_VEC_CHUNK_TILES);
 }();
 // test hooks (hbec_set_vec_chunk_tiles, hbec_set_vec_grid_cap): launch size
-// and grid of the aligned strided kernels, so that kilobytes of data walk
-// several rows of a few blocks and cross launch boundaries; 0 = the defaults
+// and grid of the aligned strided kernels, the packed one included, so that
+// kilobytes of data walk several rows of a few blocks and cross launch
+// boundaries; 0 = the defaults (g_vec_chunk_tiles, for the packed kernel
+// g_chunk_tiles, and no cap)
 static std::atomic<uint64_t> g_vec_chunk_override{0};
 static std::atomic<int> g_vec_grid_cap{0};
 static uint64_t vec_chunk_tiles() {
     const uint64_t v = g_vec_chunk_override.load(std::memory_order_relaxed);
     return v ? v : g_vec_chunk_tiles;
+}
+static uint64_t packed_chunk_tiles() {
+    const uint64_t v = g_vec_chunk_override.load(std::memory_order_relaxed);
+    return v ? v : g_chunk_tiles;
 }
 static int vec_grid_cap(int grid) {
     const int cap = g_vec_grid_cap.load(std::memory_order_relaxed);
@@ -479,6 +485,25 @@ enum ApplyRoute { kArPacked, kArVec, kArOdd, kArUnaligned, kArWide, kArCount };
 static std::atomic<uint64_t> g_apply_routes[kArCount];
 static void count_apply(ApplyRoute r) { g_apply_routes[r].fetch_add(1, std::memory_order_relaxed); }
 
+// Launches since load of the aligned strided apply kernels, by kernel
+// (hbec_vec_kernel_stats).  launch_vec picks the kernel itself; vec_kernel_of
+// names its pick from the predicates of kernels.hip that the tile size and the
+// block size of the same launch come from (vec_tile_bytes, vec_block_threads):
+// the runtime-K kernel when there is no unrolled instance or it is forced,
+// else a pipelined one for a first column pass over at least one pipelined
+// tile (gf_apply_vec_pipe2 up to HBEC_PIPE_V2_MAXK inputs), else gf_apply_vec.
+enum VecKernel { kVkPacked, kVkPipe2, kVkPipe, kVkVec, kVkStream, kVkCount };
+static std::atomic<uint64_t> g_vec_launches[kVkCount];
+static VecKernel vec_kernel_of(int K, int R, uint64_t shard_len, bool accumulate, int force_stream) {
+    if (is_streaming_shape(K, R, force_stream)) return kVkStream;
+    if (accumulate || !is_pipe_shape(K, R, shard_len, force_stream)) return kVkVec;
+    return K <= HBEC_PIPE_V2_MAXK ? kVkPipe2 : kVkPipe;
+}
+static hipError_t counted(VecKernel which, hipError_t e) {
+    if (e == hipSuccess) g_vec_launches[which].fetch_add(1, std::memory_order_relaxed);
+    return e;
+}
+
 int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, const hbec_view* out,
                 uint64_t n_obj, uint64_t shard_len, hipStream_t stream) {
     if (rows <= 0 || n_obj == 0 || shard_len == 0) return HBEC_OK;
@@ -522,11 +547,12 @@ int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, 
                 if (g_blocks_per_cu_override > 0) per_cu = g_blocks_per_cu_override;
                 const uint64_t spo = shard_len / 16;
                 const uint64_t te = (uint64_t)packed_tile_elems(K);
-                const uint64_t max_obj = packed_objs_per_launch(spo, te, g_chunk_tiles);
+                const uint64_t max_obj = packed_objs_per_launch(spo, te, packed_chunk_tiles());
                 rc = for_object_chunks(a, K, R, n_obj, max_obj, [&](PassArgs& b, uint64_t) {
                     set_packed_tiles(b, spo, te);
-                    const int grid = grid_blocks(b.n_tiles, kPipeBlockThreads / 64, (uint64_t)cus * per_cu);
-                    return launched(launch_packed(K, R, b, apply_grid_cap(grid), stream), "launch gf_apply_packed");
+                    const int grid = vec_grid_cap(grid_blocks(b.n_tiles, kPipeBlockThreads / 64, (uint64_t)cus * per_cu));
+                    return launched(counted(kVkPacked, launch_packed(K, R, b, apply_grid_cap(grid), stream)),
+                                    "launch gf_apply_packed");
                 });
             } else if (vec && !to_rec) {
                 // the pipelined instance's occupancy only for the first column pass
@@ -543,7 +569,9 @@ int apply_views(int rows, int cols, const uint8_t* coeffs, const hbec_view* in, 
                 rc = for_object_chunks(a, K, R, n_obj, max_obj, [&](PassArgs& b, uint64_t) {
                     set_tiles(b, tpo);
                     const int grid = vec_grid_cap(grid_blocks(b.n_tiles, wpb, (uint64_t)cus * per_cu));
-                    return launched(launch_vec(K, R, b, apply_grid_cap(grid), stream, force_stream), "launch gf_apply_vec");
+                    return launched(counted(vec_kernel_of(K, R, shard_len, c0 > 0, force_stream),
+                                            launch_vec(K, R, b, apply_grid_cap(grid), stream, force_stream)),
+                                    "launch gf_apply_vec");
                 });
             } else if (odd_enabled() && cols <= kOddMaxK && pos32_shard(shard_len)) {
                 // any alignment / length: gf_odd (odd.hip), passes of <= 8 inputs,
@@ -1656,6 +1684,15 @@ int hbec_apply_route_stats(hbec_apply_routes* out) {
         if (!out) return fail(HBEC_ERR_INVALID_ARG, "null argument");
         auto n = [](hbec::ApplyRoute r) { return hbec::g_apply_routes[r].load(std::memory_order_relaxed); };
         *out = {n(hbec::kArPacked), n(hbec::kArVec), n(hbec::kArOdd), n(hbec::kArUnaligned), n(hbec::kArWide)};
+        return HBEC_OK;
+    });
+}
+
+int hbec_vec_kernel_stats(uint64_t* packed, uint64_t* pipe2, uint64_t* pipe, uint64_t* vec, uint64_t* stream) {
+    return hbec::guarded("hbec_vec_kernel_stats", [&]() -> int {
+        uint64_t* const out[hbec::kVkCount] = {packed, pipe2, pipe, vec, stream};
+        for (int i = 0; i < hbec::kVkCount; ++i)
+            if (out[i]) *out[i] = hbec::g_vec_launches[i].load(std::memory_order_relaxed);
         return HBEC_OK;
     });
 }

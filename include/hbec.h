@@ -705,12 +705,20 @@ int hbec_set_force_stream(int on);
 int hbec_set_odd_chunk_tiles(uint64_t tiles);
 /* Test hooks, likewise process-wide: tiles per launch (at most 2^31; 0 = the
  * tuned default) and a cap on the grid in blocks (0 = none, negative is
- * refused) of the aligned strided kernels, so a test drives the pipelined
- * kernels with 1-8 blocks over several rows and launches on kilobytes of data.
- * hbec_vec_launch_config reports the values in force. */
+ * refused) of the aligned strided kernels, gf_apply_packed included, so a test
+ * drives the pipelined and packed kernels with 1-8 blocks over several rows
+ * and launches on kilobytes of data.  hbec_vec_launch_config reports the
+ * values in force (with no override, the pipelined kernels' default; the
+ * packed kernel's own default is 1 Mi tiles). */
 int hbec_set_vec_chunk_tiles(uint64_t tiles);
 int hbec_set_vec_grid_cap(int blocks);
 int hbec_vec_launch_config(uint64_t* chunk_tiles, int* grid_cap);
+/* Launches since load of the 16-B-aligned strided apply kernels, by the kernel
+ * launched: gf_apply_packed, gf_apply_vec_pipe2, gf_apply_vec_pipe,
+ * gf_apply_vec (the accumulate pass of more than 16 inputs) and
+ * gf_apply_vec_stream.  hbec_apply_route_stats counts the last four as one.
+ * Any pointer may be NULL; needs no device. */
+int hbec_vec_kernel_stats(uint64_t* packed, uint64_t* pipe2, uint64_t* pipe, uint64_t* vec, uint64_t* stream);
 /* Store depth of the pipelined kernel gf_apply_vec_pipe2 for a k x r pass
  * (tiles whose outputs a wave stores in one burst; 1 for every other kernel)
  * and whether its blocks walk runs of consecutive tiles. */
