@@ -60,6 +60,10 @@ class Object(C.Structure):
     _fields_ = [("data", C.c_void_p), ("parity", C.c_void_p), ("shard_len", C.c_uint64)]
 
 
+class FileObject(C.Structure):
+    _fields_ = [("files", C.POINTER(C.c_void_p)), ("content_length", C.c_uint64)]
+
+
 READ_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)
 
@@ -108,6 +112,9 @@ _SIG = [
     ("hbec_fill_splitmix", C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P]),
     ("hbec_plan_stripes", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64, C.POINTER(_P)]),
     ("hbec_plan_objects", C.c_int, [_P, C.POINTER(Object), C.c_uint64, C.POINTER(_P)]),
+    ("hbec_plan_shards", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(_P)]),
+    ("hbec_plan_files", C.c_int,
+     [_P, C.POINTER(FileObject), C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(_P)]),
     ("hbec_plan_free", None, [_P]),
     ("hbec_plan_info", C.c_int,
      [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -178,6 +185,8 @@ _SIG = [
     ("hbec_odd_edge_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_odd_record_cache", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_ec_shard_length", C.c_int64, [C.c_int64, C.c_int64]),
+    ("hbec_ec_stripe_count", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64)]),
+    ("hbec_ec_stripe_shard_length", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("hbec_ec_split", C.c_int, [C.c_int, C.c_int, READ_FN, _P, C.c_int, C.c_int64, WRITE_FN, C.POINTER(_P)]),
     ("hbec_ec_reconstruct", C.c_int,
      [C.c_int, C.c_int, READ_FN, C.POINTER(_P), C.c_int, C.c_int64, WRITE_FN, C.POINTER(_P),

@@ -150,12 +150,57 @@ class StripePlan:
     back to back (ecSplit's databuf layout).  Buffers must outlive the plan's
     queued work."""
 
-    def __init__(self, enc: Encoder, stripes=None, objects=None):
+    def __init__(self, enc: Encoder, stripes=None, objects=None, shards=None, files=None, chunk_size=None):
         """stripes = [(base, shard_len)] (ecSplit databuf layout), or
         objects = [(data, parity, shard_len)] (data and parity in separate
-        regions, hbec_plan_objects)."""
+        regions, hbec_plan_objects), or
+        shards = [([address] * (k+m), shard_len)]: every shard of an entry named,
+        anywhere and at any alignment (hbec_plan_shards), or
+        files = [([address] * (k+m), content_length)] with chunk_size: objects
+        given as their k+m shard files, as ecSplit writes them; the library cuts
+        them into entries, one per stripe (hbec_plan_files), and
+        ``object_start`` (numpy uint32, n_objects + 1) says which: object g is
+        entries [object_start[g], object_start[g+1]).  It is what hash_files
+        takes, and the arguments indexed by entry (present, flags, where) have
+        object_start[-1] rows.
+        A shards or files plan takes every call of the other plans; encode,
+        reconstruct and verify run the kernels of their _mixed forms, which are
+        slower than a stripe or object plan's."""
         self.enc = enc
         self._h = C.c_void_p()
+        n = enc.DataShards + enc.ParityShards
+        if shards is not None or files is not None:
+            import numpy as np
+
+            if (shards is not None) == (files is not None) or stripes is not None or objects is not None:
+                raise ValueError("give one of stripes, objects, shards, files")
+            if files is not None and chunk_size is None:
+                raise ValueError("files needs chunk_size")
+            entries = shards if shards is not None else files
+            ptrs = (C.c_void_p * max(1, len(entries) * n))()
+            lens = np.zeros(max(1, len(entries)), np.uint64)
+            for i, (addrs, length) in enumerate(entries):
+                if len(addrs) != n:
+                    raise ValueError("every entry needs k+m addresses")
+                for j, a in enumerate(addrs):
+                    ptrs[i * n + j] = a
+                lens[i] = length
+            if shards is not None:
+                self._n = len(shards)
+                check(N.lib().hbec_plan_shards(enc.handle, ptrs, lens.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               len(shards), C.byref(self._h)))
+                return
+            objs = (N.FileObject * max(1, len(files)))()
+            for i in range(len(files)):
+                objs[i].files = C.cast(C.byref(ptrs, i * n * C.sizeof(C.c_void_p)), C.POINTER(C.c_void_p))
+                objs[i].content_length = int(lens[i])
+            starts = np.zeros(len(files) + 1, np.uint32)
+            self._n = 0
+            check(N.lib().hbec_plan_files(enc.handle, objs, len(files), int(chunk_size),
+                                          starts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(self._h)))
+            self.object_start = starts
+            self._n = int(starts[-1])
+            return
         self._n = len(objects) if objects is not None else len(stripes)
         if objects is not None:
             arr = (N.Object * max(1, len(objects)))()

@@ -4,6 +4,7 @@
 //
 //   hbec_ec_shard_length  <- ecShardLength   ecutils.go:14-24
 //   hbec_ec_split         <- ecSplit         ecutils.go:26-72
+//   hbec_ec_stripe_count, hbec_ec_stripe_shard_length <- its loop and ecutils.go:85-92
 //   hbec_ec_reconstruct   <- ecReconstruct   ecutils.go:74-132
 //   hbec_ec_glue          <- ecGlue          ecutils.go:134-186
 //   hbec_parse_ec_scheme  <- parseECScheme   ecobj.go:82-98
@@ -27,6 +28,7 @@
 
 #include "../../include/hbec.h"
 #include "internal.h"
+#include "shardplan.h"
 
 using hbec::fail;
 
@@ -253,6 +255,21 @@ int64_t hbec_ec_shard_length(int64_t length, int64_t data_shards) {
     int64_t s = length / shards;
     if (length % shards > 0) s += 1;
     return s;
+}
+
+// ecSplit's stripe arithmetic (ecutils.go:38-58, 85-92; shardplan.h).  Host only.
+int hbec_ec_stripe_count(int64_t content_length, int64_t data_shards, int64_t chunk_size, uint64_t* n_stripes) {
+    if (!n_stripes || data_shards < 1 || chunk_size < 1) return HBEC_ERR_INVALID_ARG;
+    *n_stripes = hbec::ec_stripe_count(content_length, data_shards, chunk_size);
+    return HBEC_OK;
+}
+
+int hbec_ec_stripe_shard_length(int64_t content_length, int64_t data_shards, int64_t chunk_size, uint64_t stripe,
+                                uint64_t* shard_len) {
+    if (!shard_len || data_shards < 1 || chunk_size < 1) return HBEC_ERR_INVALID_ARG;
+    if (stripe >= hbec::ec_stripe_count(content_length, data_shards, chunk_size)) return HBEC_ERR_INVALID_ARG;
+    *shard_len = hbec::ec_stripe_shard_length(content_length, data_shards, chunk_size, stripe);
+    return HBEC_OK;
 }
 
 // ecSplit (ecutils.go:26-72).

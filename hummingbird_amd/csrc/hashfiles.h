@@ -85,9 +85,10 @@ inline uint64_t files_chains(const std::vector<MSrc>& src, const uint32_t* objec
 // them passes the filter (filter == nullptr, or filter[entry] & filter_bits);
 // digest to digests + (g n + shard) 16 when digests is given; bad[g] |=
 // 1 << shard when expected is given and differs there.
+// rows: the records are a shards plan's (a = the entry's address row, shardplan.h).
 hipError_t launch_md5_files(const HRec* recs, const uint32_t* object_start, const FChain* chains, uint64_t n_chains,
                             int k, int n, const uint32_t* filter, uint32_t filter_bits, const uint8_t* expected,
-                            uint8_t* digests, uint32_t* bad, hipStream_t stream);
+                            uint8_t* digests, uint32_t* bad, hipStream_t stream, bool rows = false);
 // One thread per source entry, after md5_files on the same stream: with g =
 // object_of[i], where[i] |= hash_where_word(sel[g], bad[g], route) for the
 // non-empty entries on the kernel route that pass the filter themselves,

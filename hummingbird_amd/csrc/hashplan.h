@@ -87,9 +87,10 @@ inline void hash_chains(const std::vector<uint32_t>& order, int n, const uint8_t
 // when its entry passes the filter (filter == nullptr, or filter[entry] &
 // filter_bits); digest to digests + (entry n + shard) 16 when digests is given;
 // bad[entry] |= 1 << shard when expected is given and differs there.
+// rows: the records are a shards plan's (a = the entry's address row, shardplan.h).
 hipError_t launch_md5_plan(const HRec* recs, const HChain* chains, uint64_t n_chains, int k, int n,
                            const uint32_t* filter, uint32_t filter_bits, const uint8_t* expected, uint8_t* digests,
-                           uint32_t* bad, hipStream_t stream);
+                           uint32_t* bad, hipStream_t stream, bool rows = false);
 // One thread per source entry, after md5_plan on the same stream: where[i] |=
 // hash_where_word(sel[i], bad[i], route) for the examined non-empty entries on
 // the kernel route, kLocSkipped for every non-empty entry on the other.

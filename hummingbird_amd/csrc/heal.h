@@ -132,9 +132,10 @@ uint32_t heal_plan_tile_bytes();
 // written, flags[entry] |= 1 on a disagreeing checked shard) and tile 0 ORs
 // kHealDone, and 2 when nothing is checked; otherwise nothing of the entry is
 // loaded and tile 0 ORs kHealUnnamed.
+// rows: the records are a shards plan's (a = the entry's address row, shardplan.h).
 hipError_t launch_heal_mixed_plan(int k, int r, const MRec* recs, const MTile* tiles, uint32_t n_tiles,
                                   const uint32_t* index_of, const uint32_t* heal_word,
                                   const uint32_t* present_bits, const uint32_t* pats, const uint32_t* where,
-                                  uint32_t* flags, int cus, hipStream_t stream);
+                                  uint32_t* flags, int cus, hipStream_t stream, bool rows = false);
 
 }  // namespace hbec

@@ -109,8 +109,9 @@ uint32_t locate_plan_tile_bytes();
 // (r >= 1: the largest count in the call) is compared, and classified where it
 // is inconsistent: where[entry] |= kLocBad | ruled-out shards.  Tile 0 of an
 // entry whose word is kVmNothing ORs kLocNothing, filtered or not.
+// rows: the records are a shards plan's (a = the entry's address row, shardplan.h).
 hipError_t launch_locate_mixed_plan(int k, int r, const MRec* recs, const MTile* tiles, uint32_t n_tiles,
                                     const uint32_t* pat_of, const uint32_t* pats, const uint32_t* flags,
-                                    uint32_t* where, int cus, hipStream_t stream);
+                                    uint32_t* where, int cus, hipStream_t stream, bool rows = false);
 
 }  // namespace hbec

@@ -97,7 +97,9 @@ inline uint32_t mp_pattern(std::vector<uint32_t>& buf, int k, const int* surv, c
 
 // Tiles [0, n_tiles) of `tiles`: codes every tile whose entry's pattern has 1..r
 // outputs (r: the largest count in the call).  K <= kOddMaxK inputs, 1 <= r <= kMaxR.
+// rows: the records are a shards plan's (a = the entry's address row, shardplan.h).
 hipError_t launch_mixed_plan(int k, int r, const MRec* recs, const MTile* tiles, uint32_t n_tiles,
-                             const uint32_t* pat_of, const uint32_t* pats, int cus, hipStream_t stream);
+                             const uint32_t* pat_of, const uint32_t* pats, int cus, hipStream_t stream,
+                             bool rows = false);
 
 }  // namespace hbec

@@ -19,10 +19,16 @@
 // stages its chain list where those calls stage their words.  The hash of
 // multi-stripe shard files (hbec_hash_plan_files; hashfiles.h, hashfiles.hip)
 // reads the same records and stages its chains and object table there too.
+// A plan whose entries name every shard (hbec_plan_shards, hbec_plan_files;
+// shardplan.h) has those records and lists only, with a row of shard addresses
+// where the others have two bases: every call with a pattern per entry takes it
+// as it takes the others, and the calls with one pattern for all run the same
+// kernels with that pattern for every entry.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -39,6 +45,7 @@
 #include "locate.h"
 #include "mixedplan.h"
 #include "repair.h"
+#include "shardplan.h"
 #include "vmixed.h"
 #include "vplan.h"
 
@@ -117,6 +124,13 @@ struct hbec_plan {
     mutable bool hash_built = false;
     mutable hbec::HRec* d_hrecs = nullptr;
     mutable std::vector<uint32_t> hash_order;
+    // shards plans (hbec_plan_shards, hbec_plan_files): shard j of source entry i
+    // is at rows[i (k + m) + j]; d_rows is the same table on the device and
+    // src[i].a the device address of row i (b = 0).
+    // No tile, unaligned or Verify records: every call runs over src.
+    bool shards = false;
+    std::vector<uint64_t> rows;
+    uint64_t* d_rows = nullptr;
 };
 
 // The gf_odd_rec records of a plan pass depend only on the plan's stripes and
@@ -228,6 +242,14 @@ int upload(const std::vector<T>& recs, T** dst, const char* what) {
         return hip_fail(e, what);
     }
     return HBEC_OK;
+}
+
+// Where shard `sh` of source entry i of a plan is (the host's copy of the rule
+// the kernels hold: two bases, or the entry's row of a shards plan).
+uint64_t shard_addr(const hbec_plan* p, uint32_t i, int sh) {
+    if (p->shards) return p->rows[(size_t)i * (size_t)(p->k + p->m) + (size_t)sh];
+    const hbec::MSrc& s = p->src[i];
+    return sh < p->k ? s.a + (uint64_t)sh * s.shard_len : s.b + (uint64_t)(sh - p->k) * s.shard_len;
 }
 
 // One pass of a plan over per-stripe records: the records of every stripe in
@@ -721,10 +743,7 @@ int stage_begin(const hbec_plan* plan, const std::vector<uint32_t>& stage, hipSt
 int reconstruct_other_entry(const hbec_plan* plan, uint32_t i, const PlanPattern& pp, hipStream_t stream) {
     const int k = plan->k;
     const hbec::MSrc& s = plan->src[i];
-    auto at = [&](int sh) {
-        const uint64_t addr = sh < k ? s.a + (uint64_t)sh * s.shard_len : s.b + (uint64_t)(sh - k) * s.shard_len;
-        return hbec_view{reinterpret_cast<void*>(addr), 0};
-    };
+    auto at = [&](int sh) { return hbec_view{reinterpret_cast<void*>(shard_addr(plan, i, sh)), 0}; };
     std::vector<hbec_view> vin((size_t)k), vout(pp.outs.size());
     for (int j = 0; j < k; ++j) vin[j] = at(pp.surv[j]);
     for (size_t q = 0; q < pp.outs.size(); ++q) vout[q] = at(pp.outs[q]);
@@ -742,11 +761,15 @@ int verify_other_entry(hbec_codec* codec, const hbec_plan* plan, uint32_t i, con
         const hipError_t e = hbec::launch_vm_or(d_flags + i, 2u, stream);
         return e == hipSuccess ? HBEC_OK : hip_fail(e, "launch gf_vm_or");
     }
-    if ((int)pp.outs.size() == m)
-        return hbec::verify_other_run(codec, hbec::VOther{s.a, s.b, s.shard_len, i}, d_flags, stream);
-    auto at = [&](int sh) {
-        return sh < k ? s.a + (uint64_t)sh * s.shard_len : s.b + (uint64_t)(sh - k) * s.shard_len;
-    };
+    if ((int)pp.outs.size() == m) {
+        if (!plan->shards) return hbec::verify_other_run(codec, hbec::VOther{s.a, s.b, s.shard_len, i}, d_flags, stream);
+        // what verify_other_run does, with the entry's own shard addresses
+        std::vector<hbec_view> v((size_t)k + m);
+        for (int sh = 0; sh < k + m; ++sh) v[sh] = {reinterpret_cast<void*>(shard_addr(plan, i, sh)), 0};
+        g_vplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
+        return hbec_verify_batch(codec, v.data(), 1, s.shard_len, d_flags + i, stream);
+    }
+    auto at = [&](int sh) { return shard_addr(plan, i, sh); };
     void* scratch = nullptr;
     int rc = hbec::scratch_alloc(pp.outs.size() * (size_t)s.shard_len, stream, &scratch);
     if (rc) return rc;
@@ -836,7 +859,8 @@ int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8
         for (uint64_t t0 = 0; rmax > 0 && t0 < plan->n_mtiles && e == hipSuccess; t0 += chunk) {
             const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
             g_mplan_launches.fetch_add(1, std::memory_order_relaxed);
-            e = hbec::launch_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats, cus, stream);
+            e = hbec::launch_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats, cus, stream,
+                                        plan->shards);
         }
         rc = stage_end(plan, stream);
         if (e != hipSuccess) return hip_fail(e, "launch gf_mixed_plan");
@@ -922,7 +946,7 @@ int verify_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* p
             const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
             g_vmplan_launches.fetch_add(1, std::memory_order_relaxed);
             e = hbec::launch_verify_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats,
-                                               d_flags, cus, stream);
+                                               d_flags, cus, stream, plan->shards);
         }
         rc = stage_end(plan, stream);
         if (e != hipSuccess) return hip_fail(e, "launch gf_verify_mixed_plan");
@@ -1024,7 +1048,7 @@ int repair_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* p
             const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
             g_rplan_launches.fetch_add(1, std::memory_order_relaxed);
             e = hbec::launch_repair_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats,
-                                               d_flags, cus, stream);
+                                               d_flags, cus, stream, plan->shards);
         }
         rc = stage_end(plan, stream);
         if (e != hipSuccess) return hip_fail(e, "launch gf_repair_mixed_plan");
@@ -1112,7 +1136,7 @@ int locate_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* p
             const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
             g_locplan_launches.fetch_add(1, std::memory_order_relaxed);
             e = hbec::launch_locate_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats,
-                                               d_flags, d_where, cus, stream);
+                                               d_flags, d_where, cus, stream, plan->shards);
         }
         rc = stage_end(plan, stream);
         if (e != hipSuccess) return hip_fail(e, "launch gf_locate_mixed_plan");
@@ -1228,7 +1252,7 @@ int heal_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* pat
             g_healplan_launches.fetch_add(1, std::memory_order_relaxed);
             e = hbec::launch_heal_mixed_plan(k, std::max(1, m), plan->d_mrecs, plan->d_mtiles + t0, nt, d_index,
                                              d_pats + h.words_at, d_pats + h.present_at, d_pats, d_where, d_flags,
-                                             cus, stream);
+                                             cus, stream, plan->shards);
         }
         rc = stage_end(plan, stream);
         if (e != hipSuccess) return hip_fail(e, "launch gf_heal_mixed_plan");
@@ -1310,7 +1334,7 @@ int hash_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* sel
     g_hashplan_launches.fetch_add(1, std::memory_order_relaxed);
     g_hashplan_chains.fetch_add(chains.size(), std::memory_order_relaxed);
     hipError_t e = hbec::launch_md5_plan(plan->d_hrecs, d_chains, chains.size(), k, n, d_filter, filter_bits,
-                                         d_expected, d_digests, d_expected ? d_bad : nullptr, stream);
+                                         d_expected, d_digests, d_expected ? d_bad : nullptr, stream, plan->shards);
     if (e == hipSuccess && d_where) {
         g_hashplan_launches.fetch_add(1, std::memory_order_relaxed);
         e = hbec::launch_hash_where(plan->d_hrecs, (uint32_t)n_src, plan->d_mstage + chain_words, d_filter,
@@ -1381,7 +1405,7 @@ int hash_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* ob
     hipError_t e = hbec::launch_md5_files(plan->d_hrecs, d_stage + objects_at,
                                           reinterpret_cast<const hbec::FChain*>(d_stage), chains.size(), k, n,
                                           d_filter, filter_bits, d_expected, d_digests,
-                                          d_expected ? d_bad : nullptr, stream);
+                                          d_expected ? d_bad : nullptr, stream, plan->shards);
     if (e == hipSuccess && d_where) {
         g_hashfiles_launches.fetch_add(1, std::memory_order_relaxed);
         e = hbec::launch_hash_files_where(plan->d_hrecs, (uint32_t)n_src, d_stage + of_at, d_stage + sel_at, d_filter,
@@ -1392,9 +1416,104 @@ int hash_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* ob
     return rc;
 }
 
+// The calls with one pattern for all (hbec_encode_plan, hbec_reconstruct_plan,
+// hbec_verify_plan) on a shards plan: the call with a pattern per entry, every
+// entry given pattern 0.
+template <class F>
+int uniform_mixed(const hbec_plan* plan, F&& call) {
+    const std::vector<uint32_t> of((size_t)plan->n_src, 0u);
+    return call(of.data());
+}
+
+// A shards plan from its table: shard j of entry e at rows[e n + j], lens[e]
+// bytes each.  Every argument error is found before the first HIP call.
+int build_shards_plan(hbec_codec* codec, std::vector<uint64_t>&& rows, const std::vector<uint64_t>& lens,
+                      hbec_plan** out) {
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
+    const uint64_t n_src = lens.size();
+    if (n_src >= (1ull << 32)) return fail(HBEC_ERR_INVALID_ARG, "plan too large (>= 2^32 entries)");
+    std::unique_ptr<hbec_plan> p(new (std::nothrow) hbec_plan());
+    if (!p) return fail(HBEC_ERR_NOMEM, "plan allocation");
+    p->k = k;
+    p->m = m;
+    p->shards = true;
+    p->n_src = n_src;
+    p->src.assign((size_t)n_src, hbec::MSrc{0, 0, 0});
+    std::vector<uint64_t> tmp;
+    for (uint64_t e = 0; e < n_src; ++e) {
+        if (lens[e] == 0) continue;
+        if (const char* why = hbec::shards_check_row(rows.data() + (size_t)e * n, n, lens[e], tmp))
+            return fail(HBEC_ERR_INVALID_ARG, std::string(why) + " (entry " + std::to_string(e) + ")");
+        p->src[e].shard_len = lens[e];
+        p->shard_bytes += lens[e];
+    }
+    p->rows = std::move(rows);
+    if (p->shard_bytes > 0) {
+        int rc = upload(p->rows, &p->d_rows, "plan shard address rows");
+        if (rc) return rc;
+        for (uint64_t e = 0; e < n_src; ++e)
+            if (lens[e]) p->src[e].a = reinterpret_cast<uint64_t>(p->d_rows + (size_t)e * n);
+    }
+    *out = p.release();
+    return HBEC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int hbec_plan_shards(hbec_codec* codec, void* const* shards, const uint64_t* shard_lens, uint64_t n_entries,
+                     hbec_plan** out) {
+    return hbec::guarded("hbec_plan_shards", [&]() -> int {
+        if (!codec || !out || !shards || !shard_lens) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *out = nullptr;
+        if (n_entries >= (1ull << 32)) return fail(HBEC_ERR_INVALID_ARG, "plan too large (>= 2^32 entries)");
+        const size_t n = (size_t)(hbec_data_shards(codec) + hbec_parity_shards(codec));
+        std::vector<uint64_t> rows((size_t)n_entries * n), lens(shard_lens, shard_lens + n_entries);
+        for (size_t i = 0; i < rows.size(); ++i) rows[i] = reinterpret_cast<uint64_t>(shards[i]);
+        return build_shards_plan(codec, std::move(rows), lens, out);
+    });
+}
+
+int hbec_plan_files(hbec_codec* codec, const hbec_file_object* objects, uint32_t n_objects, uint64_t chunk_size,
+                    uint32_t* object_start, hbec_plan** out) {
+    return hbec::guarded("hbec_plan_files", [&]() -> int {
+        if (!codec || !out || !object_start || (n_objects && !objects))
+            return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *out = nullptr;
+        if (chunk_size == 0 || chunk_size > (uint64_t)INT64_MAX)
+            return fail(HBEC_ERR_INVALID_ARG, "chunk_size must be 1 .. 2^63 - 1");
+        const int k = hbec_data_shards(codec), n = k + hbec_parity_shards(codec);
+        uint64_t total = 0;
+        for (uint32_t g = 0; g < n_objects; ++g) {
+            const hbec_file_object& o = objects[g];
+            if (o.content_length > (uint64_t)INT64_MAX)
+                return fail(HBEC_ERR_INVALID_ARG, "content_length above 2^63 - 1 (object " + std::to_string(g) + ")");
+            const uint64_t c = hbec::ec_stripe_count((int64_t)o.content_length, k, (int64_t)chunk_size);
+            if (c && !o.files) return fail(HBEC_ERR_INVALID_ARG, "null files (object " + std::to_string(g) + ")");
+            for (int j = 0; c && j < n; ++j)
+                if (!o.files[j])
+                    return fail(HBEC_ERR_INVALID_ARG, "null file pointer in an object with content_length > 0 "
+                                                      "(object " + std::to_string(g) + ")");
+            total += c;
+            if (total > 0xFFFFFFFFull) return fail(HBEC_ERR_INVALID_ARG, "more than 2^32 - 1 entries");
+        }
+        std::vector<uint64_t> rows, lens;
+        rows.reserve((size_t)total * n);
+        lens.reserve((size_t)total);
+        object_start[0] = 0;
+        for (uint32_t g = 0; g < n_objects; ++g) {
+            const hbec_file_object& o = objects[g];
+            const uint64_t c = hbec::ec_stripe_count((int64_t)o.content_length, k, (int64_t)chunk_size);
+            for (uint64_t t = 0; t < c; ++t) {
+                lens.push_back(hbec::ec_stripe_shard_length((int64_t)o.content_length, k, (int64_t)chunk_size, t));
+                for (int j = 0; j < n; ++j) rows.push_back(reinterpret_cast<uint64_t>(o.files[j]) + t * chunk_size);
+            }
+            object_start[g + 1] = (uint32_t)lens.size();
+        }
+        return build_shards_plan(codec, std::move(rows), lens, out);
+    });
+}
 
 int hbec_plan_stripes(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n, hbec_plan** out) {
     return hbec::guarded("hbec_plan_stripes", [&]() -> int {
@@ -1590,6 +1709,7 @@ void hbec_plan_free(hbec_plan* plan) {
     if (plan->d_mstage) (void)hipFree(plan->d_mstage);
     if (plan->d_heal) (void)hipFree(plan->d_heal);
     if (plan->d_hrecs) (void)hipFree(plan->d_hrecs);
+    if (plan->d_rows) (void)hipFree(plan->d_rows);
     if (plan->mp_ev) (void)hipEventDestroy(plan->mp_ev);
     for (uint32_t* l : plan->d_lists)
         if (l) (void)hipFree(l);
@@ -1614,6 +1734,15 @@ int hbec_encode_plan(hbec_codec* codec, const hbec_plan* plan, void* hip_stream)
         const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
         if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
         if (m == 0) return HBEC_OK;
+        if (plan->shards) {
+            // data present, parity missing: that mask's decode rows are the parity rows
+            std::vector<uint8_t> mask((size_t)k + m, 0);
+            std::fill(mask.begin(), mask.begin() + k, (uint8_t)1);
+            return uniform_mixed(plan, [&](const uint32_t* of) {
+                return reconstruct_plan_mixed(codec, plan, mask.data(), 1, of, false,
+                                              static_cast<hipStream_t>(hip_stream));
+            });
+        }
         std::vector<uint8_t> mat((size_t)(k + m) * k);
         hbec_matrix(codec, mat.data());
         std::vector<uint8_t> rows(mat.begin() + (size_t)k * k, mat.end());
@@ -1637,6 +1766,11 @@ int hbec_reconstruct_plan(hbec_codec* codec, const hbec_plan* plan, const uint8_
         }
         if (n_present == n || (data_only && data_present == k)) return HBEC_OK;
         if (n_present < k) return fail(HBEC_ERR_TOO_FEW_SHARDS, "too few shards given");
+        if (plan->shards)
+            return uniform_mixed(plan, [&](const uint32_t* of) {
+                return reconstruct_plan_mixed(codec, plan, present, 1, of, data_only != 0,
+                                              static_cast<hipStream_t>(hip_stream));
+            });
         std::vector<int> surv(k), outs(n);
         std::vector<uint8_t> rows((size_t)n * k);
         int n_out = 0;
@@ -1839,6 +1973,13 @@ int hbec_verify_plan(hbec_codec* codec, const hbec_plan* plan, uint32_t* d_flags
         if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
         if (m == 0 || plan->shard_bytes == 0) return HBEC_OK;
         hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        if (plan->shards) {
+            // every shard present: the m parity shards are the checked ones, bit 0 only
+            const std::vector<uint8_t> mask((size_t)k + m, 1);
+            return uniform_mixed(plan, [&](const uint32_t* of) {
+                return verify_plan_mixed(codec, plan, mask.data(), 1, of, d_flags, stream);
+            });
+        }
         if (plan->n_tiles > 0 && hbec::vp_tiles_shape(k, m)) {
             // the aligned stripes' tile records (the other shapes have a VRec each)
             std::vector<uint8_t> mat((size_t)(k + m) * k);

@@ -60,8 +60,9 @@ uint32_t repair_plan_tile_bytes();
 // total (r >= 1: the largest total in the call) rebuilds its r_o outputs and
 // ORs 1 into flags[entry] when one of its r_c checked shards differs from what
 // the survivors imply; tile 0 of an entry whose word has r_c == 0 ORs 2.
+// rows: the records are a shards plan's (a = the entry's address row, shardplan.h).
 hipError_t launch_repair_mixed_plan(int k, int r, const MRec* recs, const MTile* tiles, uint32_t n_tiles,
                                     const uint32_t* pat_of, const uint32_t* pats, uint32_t* flags, int cus,
-                                    hipStream_t stream);
+                                    hipStream_t stream, bool rows = false);
 
 }  // namespace hbec

@@ -9,6 +9,7 @@
 #include "gf_device.h"
 #include "kernels.h"
 #include "mixedplan.h"
+#include "shard_rows.h"
 #include "unaligned_tile.h"
 
 namespace hbec {
@@ -19,8 +20,9 @@ namespace hbec {
 // mp_build writes: the output rows start from it and not from a literal, because
 // with literal zeros beside loaded rows the compiler allocates 15 to 57 VGPRs
 // more than for rows that all start alike (132 against 116 at (1, 1), 209
-// against 152 at (1, 3): a wave per SIMD less at both).
-template <int RO, int RC>
+// against 152 at (1, 3): a wave per SIMD less at both).  ROWS: the entry names
+// every shard (shard_rows.h).
+template <int RO, int RC, bool ROWS = false>
 __device__ __forceinline__ void repair_tile(int K, uint64_t a, uint64_t b, uint64_t S, uint64_t p0,
                                             const uint32_t* __restrict__ p, uint32_t lane, uint32_t* flag,
                                             uint32_t zero) {
@@ -30,7 +32,7 @@ __device__ __forceinline__ void repair_tile(int K, uint64_t a, uint64_t b, uint6
     const uint64_t s_lo = (uint64_t)p[0] | ((uint64_t)p[1] << 32);  // survivors 0..7
     const uint32_t s_hi = p[2], so = p[3];
     const uint32_t k = (uint32_t)K;
-    auto shard = [=](uint32_t i) { return i < k ? a + (uint64_t)i * S : b + (uint64_t)(i - k) * S; };
+    auto shard = [=](uint32_t i) { return shard_at<ROWS>(a, b, S, k, i); };
     auto in_base = [=](int j) {
         return shard((j < 8 ? (uint32_t)(s_lo >> (8 * j)) : s_hi >> (8 * (j - 8))) & 0xFFu);
     };

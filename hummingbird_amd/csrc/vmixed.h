@@ -60,9 +60,10 @@ uint32_t verify_mixed_plan_tile_bytes();
 // Tiles [0, n_tiles) of `tiles`: every tile whose entry's word has 1..r checked
 // shards (r >= 1: the largest count in the call) is compared and ORs 1 into
 // flags[entry] on a mismatch; tile 0 of an entry whose word is kVmNothing ORs 2.
+// rows: the records are a shards plan's (a = the entry's address row, shardplan.h).
 hipError_t launch_verify_mixed_plan(int k, int r, const MRec* recs, const MTile* tiles, uint32_t n_tiles,
                                     const uint32_t* pat_of, const uint32_t* pats, uint32_t* flags, int cus,
-                                    hipStream_t stream);
+                                    hipStream_t stream, bool rows = false);
 // the other route: *flag |= 1 when x[0, n) != y[0, n);  *flag |= bits
 hipError_t launch_vm_compare(const void* x, const void* y, uint64_t n, uint32_t* flag, int cus, hipStream_t stream);
 hipError_t launch_vm_or(uint32_t* flag, uint32_t bits, hipStream_t stream);

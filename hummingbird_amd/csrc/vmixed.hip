@@ -25,6 +25,7 @@
 
 #include "gf_device.h"
 #include "kernels.h"
+#include "shard_rows.h"
 #include "unaligned_tile.h"
 #include "vmixed.h"
 
@@ -37,8 +38,9 @@
 namespace hbec {
 
 // One tile of a stripe whose mask has R checked shards.  Every capture is a
-// value in SGPRs, as in mixed_plan_tile.
-template <int R>
+// value in SGPRs, as in mixed_plan_tile.  ROWS: the entry names every shard
+// (shard_rows.h).
+template <int R, bool ROWS = false>
 __device__ __forceinline__ void verify_mixed_tile(int K, uint64_t a, uint64_t b, uint64_t S, uint64_t p0,
                                                   const uint32_t* __restrict__ p, uint32_t lane, uint32_t* flag) {
     constexpr int U = kUnalignedU;
@@ -46,7 +48,7 @@ __device__ __forceinline__ void verify_mixed_tile(int K, uint64_t a, uint64_t b,
     const uint64_t s_lo = (uint64_t)p[0] | ((uint64_t)p[1] << 32);  // survivors 0..7
     const uint32_t s_hi = p[2], so = p[3];
     const uint32_t k = (uint32_t)K;
-    auto shard = [=](uint32_t i) { return i < k ? a + (uint64_t)i * S : b + (uint64_t)(i - k) * S; };
+    auto shard = [=](uint32_t i) { return shard_at<ROWS>(a, b, S, k, i); };
     auto in_base = [=](int j) {
         return shard((j < 8 ? (uint32_t)(s_lo >> (8 * j)) : s_hi >> (8 * (j - 8))) & 0xFFu);
     };
@@ -166,7 +168,58 @@ __global__ __launch_bounds__(kBlockThreads) void gf_verify_mixed_plan(const MRec
     }
 }
 
-static const void* verify_mixed_plan_kernel(int r) {
+// The same walk over a shards plan's records: recs[e].a is the entry's row of shard
+// addresses (shard_rows.h).  The text is gf_verify_mixed_plan's, word for word, with the
+// tiles' ROWS flag set.  It is not shared through a function: wrapping the walk
+// moved the register counts of existing instances (gf_heal_mixed_plan<4> from 161
+// to 152 VGPRs, md5_plan from 92 to 96), and those are pinned.
+template <int RMAX>
+__global__ __launch_bounds__(kBlockThreads) void gf_verify_mixed_plan_rows(const MRec* __restrict__ recs,
+                                                                           const MTile* __restrict__ tiles,
+                                                                           uint32_t n_tiles,
+                                                                           const uint32_t* __restrict__ pat_of,
+                                                                           const uint32_t* __restrict__ pats, int K,
+                                                                           uint32_t* flags) {
+    constexpr uint32_t T = (uint32_t)kUnalignedU * kUnalignedWindow;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave =
+        __builtin_amdgcn_readfirstlane(xcd_block() * (kBlockThreads / 64) + (threadIdx.x >> 6));
+    const uint32_t nwaves = gridDim.x * (kBlockThreads / 64);
+    for (uint32_t t = wave; t < n_tiles; t += nwaves) {
+        const MTile e = tiles[t];
+        const uint32_t w = pat_of[e.rec];
+        const uint32_t r = w >> kMPatShift;  // wave-uniform
+        if (r == 0u) {
+            // exactly k present: nothing to check, said once per entry; nothing loaded
+            if (w == kVmNothing && e.ti == 0u && lane == 0u) atomicOr(flags + e.rec, 2u);
+            continue;
+        }
+        if (r > (uint32_t)RMAX) continue;
+        const uint64_t a = recs[e.rec].a, b = recs[e.rec].b;
+        const uint64_t S = recs[e.rec].shard_len;
+        const uint32_t* p = pats + (size_t)(w & kMPatMask) * 4u;
+        const uint64_t p0 = (uint64_t)e.ti * T;
+        uint32_t* flag = flags + e.rec;
+        if (r == 1u) verify_mixed_tile<1, true>(K, a, b, S, p0, p, lane, flag);
+        if constexpr (RMAX >= 2)
+            if (r == 2u) verify_mixed_tile<2, true>(K, a, b, S, p0, p, lane, flag);
+        if constexpr (RMAX >= 3)
+            if (r == 3u) verify_mixed_tile<3, true>(K, a, b, S, p0, p, lane, flag);
+        if constexpr (RMAX >= 4)
+            if (r == 4u) verify_mixed_tile<4, true>(K, a, b, S, p0, p, lane, flag);
+    }
+}
+
+static const void* verify_mixed_plan_kernel(int r, bool rows) {
+    if (rows) {
+        switch (r) {
+            case 1: return reinterpret_cast<const void*>(&gf_verify_mixed_plan_rows<1>);
+            case 2: return reinterpret_cast<const void*>(&gf_verify_mixed_plan_rows<2>);
+            case 3: return reinterpret_cast<const void*>(&gf_verify_mixed_plan_rows<3>);
+            case 4: return reinterpret_cast<const void*>(&gf_verify_mixed_plan_rows<4>);
+        }
+        return nullptr;
+    }
     switch (r) {
         case 1: return reinterpret_cast<const void*>(&gf_verify_mixed_plan<1>);
         case 2: return reinterpret_cast<const void*>(&gf_verify_mixed_plan<2>);
@@ -180,16 +233,16 @@ uint32_t verify_mixed_plan_tile_bytes() { return (uint32_t)kUnalignedU * kUnalig
 
 hipError_t launch_verify_mixed_plan(int k, int r, const MRec* recs, const MTile* tiles, uint32_t n_tiles,
                                     const uint32_t* pat_of, const uint32_t* pats, uint32_t* flags, int cus,
-                                    hipStream_t stream) {
-    const void* fn = verify_mixed_plan_kernel(r);
+                                    hipStream_t stream, bool rows) {
+    const void* fn = verify_mixed_plan_kernel(r, rows);
     if (!fn || k < 1 || k > kOddMaxK || cus < 1) return hipErrorInvalidValue;
     if (n_tiles == 0) return hipSuccess;
-    static std::atomic<int> occ[kMaxR + 1] = {};  // blocks per CU, asked once per instance
-    int per_cu = occ[r].load(std::memory_order_relaxed);
+    static std::atomic<int> occ[2][kMaxR + 1] = {};  // blocks per CU, asked once per instance
+    int per_cu = occ[rows][r].load(std::memory_order_relaxed);
     if (per_cu == 0) {
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlockThreads, 0);
         if (e != hipSuccess) return e;
-        occ[r].store(std::max(1, per_cu), std::memory_order_relaxed);
+        occ[rows][r].store(std::max(1, per_cu), std::memory_order_relaxed);
     }
     constexpr uint64_t wpb = kBlockThreads / 64;
     const uint64_t grid =

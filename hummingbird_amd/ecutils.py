@@ -69,6 +69,24 @@ def ec_shard_length(length: int, data_shards: int) -> int:
     return int(N.lib().hbec_ec_shard_length(int(length), int(data_shards)))
 
 
+def ec_stripe_count(content_length: int, data_shards: int, chunk_size: int) -> int:
+    """Stripes ecSplit cuts an object into, data_shards * chunk_size bytes at a
+    time (ecutils.go:38-58; hbec_ec_stripe_count).  Host only."""
+    n = C.c_uint64()
+    check(N.lib().hbec_ec_stripe_count(int(content_length), int(data_shards), int(chunk_size), C.byref(n)))
+    return n.value
+
+
+def ec_stripe_shard_length(content_length: int, data_shards: int, chunk_size: int, stripe: int) -> int:
+    """Shard length of one stripe of such an object: chunk_size while
+    data_shards * chunk_size bytes or more remain, else the rest over
+    data_shards, rounded up (ecutils.go:85-92; hbec_ec_stripe_shard_length)."""
+    n = C.c_uint64()
+    check(N.lib().hbec_ec_stripe_shard_length(int(content_length), int(data_shards), int(chunk_size), int(stripe),
+                                              C.byref(n)))
+    return n.value
+
+
 def ec_split(data_chunks, parity_chunks, fp, chunk_size, content_length, writers):
     ids = _register([fp, *writers])
     try:

@@ -613,6 +613,69 @@ int hbec_hash_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_
  * given), chains listed, and segments those chains walk (non-empty entries, once per chain) */
 int hbec_hash_files_stats(uint64_t* kernel_launches, uint64_t* chains, uint64_t* segments);
 
+/* ---------------------------------------------------------------------------
+ * Shards plans: a plan whose entries name every shard, klauspost's [][]byte
+ * boundary.  Shard i of entry e is at shards[e * (k+m) + i] (a device address),
+ * shard_lens[e] bytes long; the shards of an entry may lie anywhere, in any
+ * order and at any alignment, each in a buffer of its own.  Both arrays are host
+ * memory and are copied before the call returns.  Entry positions, zero-length
+ * entries (their pointers are not looked at) and hbec_plan_free are those of the
+ * other two constructors.
+ * Every plan call takes such a plan.  The calls with a pattern per entry
+ * (hbec_reconstruct_plan_mixed, hbec_verify_plan_mixed, hbec_repair_plan_mixed,
+ * hbec_locate_plan_mixed, hbec_heal_plan_mixed, hbec_hash_plan_mixed,
+ * hbec_hash_plan_files) keep their contract word for word, as on a stripe plan
+ * holding the same bytes: one launch for k <= 12 with m <= 4, the per-stripe
+ * route (HBEC_LOC_SKIPPED from locate, hash and heal) for the other shapes and
+ * for shards of 2^31 - 64 KiB bytes or more, and the same stats counters.
+ * hbec_encode_plan runs hbec_reconstruct_plan_mixed's kernel with one mask for
+ * every entry, data present and parity missing, and hbec_reconstruct_plan runs
+ * it with the given mask: both count in hbec_mixed_plan_stats.  hbec_verify_plan
+ * runs hbec_verify_plan_mixed's kernel with every shard present (bit 0 only,
+ * never bit 1; nothing launched for m = 0) and counts in
+ * hbec_verify_mixed_plan_stats.  Those kernels reach 53-56 % of the HBM peak
+ * where the plan encode kernels of a stripe or object plan reach 67-76 %
+ * (DESIGN.md 4l): a caller who can keep its stripes in a databuf, or its parity
+ * in an arena, should build that plan instead.
+ * hbec_plan_info reports n_tiles = 0, tile_bytes = 0, n_fallback = 0 and
+ * shard_bytes = the sum of shard_lens.
+ * The address rows live in device memory, n_entries * (k+m) * 8 bytes,
+ * allocated here.
+ * Errors, all HBEC_ERR_INVALID_ARG and all found before the first device call:
+ * a null argument (for n_entries = 0 too); 2^32 entries or more; a null shard
+ * pointer in an entry with shard_len > 0; two shards of one entry whose byte
+ * ranges overlap (ranges that touch do not).  Shards of different entries may
+ * overlap as far as the caller can answer for it, as with the other plans.
+ * ------------------------------------------------------------------------- */
+int hbec_plan_shards(hbec_codec* codec, void* const* shards, const uint64_t* shard_lens, uint64_t n_entries,
+                     hbec_plan** out);
+/* Objects given as their k+m shard FILES, as ecSplit writes them and a repair
+ * or an audit fetches them (ecutils.go:38-70): file j is shard j of every
+ * stripe of the object, appended.  The library writes the entries: stripe t of
+ * an object of content_length L has shard length S_t = chunk_size while
+ * k * chunk_size bytes or more remain, else ceil(remaining / k)
+ * (hbec_ec_stripe_shard_length), and its shard j is at files[j] + t * chunk_size.
+ * An object of L = 0 has no entries.  object_start (host, n_objects + 1 words)
+ * is filled with the prefix sums of the stripe counts: object g is the plan's
+ * entries [object_start[g], object_start[g + 1]), which is what
+ * hbec_hash_plan_files takes, and what sizes the arrays indexed by entry
+ * (pattern_of, d_flags, d_where).  The plan is a shards plan in every respect.
+ * Each file must hold ceil(L / k) bytes, the sum of its S_t; the call cannot
+ * check that.  To read the data shards out of the contiguous object instead
+ * (stripe t's at object + t * k * chunk_size) use hbec_plan_shards: ecSplit
+ * zero-pads the last stripe to a multiple of k, and those bytes are the
+ * caller's to provide.
+ * Errors, all HBEC_ERR_INVALID_ARG and all found before the first device call:
+ * a null codec, object_start or out, null objects with n_objects > 0;
+ * chunk_size = 0; more than 2^32 - 1 entries; a null files array or file
+ * pointer in an object with L > 0; files of one object that overlap. */
+typedef struct {
+    void* const* files;      /* k+m device addresses (host array) */
+    uint64_t content_length; /* L, the object's bytes */
+} hbec_file_object;
+int hbec_plan_files(hbec_codec* codec, const hbec_file_object* objects, uint32_t n_objects, uint64_t chunk_size,
+                    uint32_t* object_start, hbec_plan** out);
+
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
  * kernel and D2H of successive chunks overlap on three streams.  Synchronous:
@@ -780,6 +843,17 @@ typedef int (*hbec_write_fn)(void* ctx, const uint8_t* buf, size_t n);
 /* ecShardLength (ecutils.go:14-24): ceil(length / k), 0 for length < 0.
  * data_shards is Go's int (64-bit), as parseECScheme returns it. */
 int64_t hbec_ec_shard_length(int64_t length, int64_t data_shards);
+/* ecSplit's stripe arithmetic, host only (ecutils.go:38-58, 85-92): the stripes
+ * an object of content_length bytes is cut into, data_shards * chunk_size bytes
+ * at a time (0 for content_length <= 0), and the shard length of stripe
+ * `stripe`: chunk_size while data_shards * chunk_size bytes or more remain,
+ * else ceil(remaining / data_shards).  The lengths of an object's stripes add
+ * up to hbec_ec_shard_length, the length of each shard file.
+ * HBEC_ERR_INVALID_ARG: a null result pointer, data_shards < 1, chunk_size < 1,
+ * stripe >= the object's stripe count. */
+int hbec_ec_stripe_count(int64_t content_length, int64_t data_shards, int64_t chunk_size, uint64_t* n_stripes);
+int hbec_ec_stripe_shard_length(int64_t content_length, int64_t data_shards, int64_t chunk_size, uint64_t stripe,
+                                uint64_t* shard_len);
 
 /* ecSplit (ecutils.go:26-72).  writers: k+m contexts, NULL = nil writer.  A
  * failing writer is dropped for the rest of the object, as in Go. */
