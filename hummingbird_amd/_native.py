@@ -87,6 +87,7 @@ _SIG = [
     ("hbec_verify_databuf", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_int)]),
     ("hbec_coalesce_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_host_md5_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_host_run_stats", C.c_int, [C.POINTER(C.c_uint64)] * 4),
     ("hbec_verify_batch", C.c_int, [_P, C.POINTER(View), C.c_uint64, C.c_uint64, _P, _P]),
     ("hbec_encode_batch", C.c_int, [_P, C.POINTER(View), C.c_uint64, C.c_uint64, _P]),
     ("hbec_reconstruct_batch", C.c_int,
@@ -176,6 +177,8 @@ _SIG = [
     ("hbec_set_vec_grid_cap", C.c_int, [C.c_int]),
     ("hbec_vec_launch_config", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     ("hbec_vec_kernel_stats", C.c_int, [C.POINTER(C.c_uint64)] * 5),
+    ("hbec_stripes_kernel_stats", C.c_int, [C.POINTER(C.c_uint64)] * 5),
+    ("hbec_set_stripes_grid_cap", C.c_int, [C.c_int]),
     ("hbec_pipe2_store_depth", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("hbec_kernel_info", C.c_int,
      [C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -741,6 +741,31 @@ def vec_kernel_stats():
     return dict(zip(("packed", "pipe2", "pipe", "vec", "stream"), (x.value for x in v)))
 
 
+STRIPES_VARIANTS = ("plain", "split", "accumulate", "mirror", "mirror_accumulate")
+
+
+def stripes_kernel_stats():
+    """Launches since load of the tiled stripes kernel gf_apply_stripes, by
+    variant (hbec_stripes_kernel_stats)."""
+    v = [C.c_uint64() for _ in STRIPES_VARIANTS]
+    check(N.lib().hbec_stripes_kernel_stats(*[C.byref(x) for x in v]))
+    return dict(zip(STRIPES_VARIANTS, (x.value for x in v)))
+
+
+def set_stripes_grid_cap(blocks: int) -> None:
+    """Test hook: at most `blocks` blocks per gf_apply_stripes launch (0 = no cap)."""
+    check(N.lib().hbec_set_stripes_grid_cap(int(blocks)))
+
+
+def host_run_stats():
+    """How the host calls cut their work since load (hbec_host_run_stats):
+    staging chunks, column pieces, zero-copy record slots, hash arena flushes."""
+    names = ("ring_chunks", "ring_pieces", "zc_record_slots", "arena_flushes")
+    v = [C.c_uint64() for _ in names]
+    check(N.lib().hbec_host_run_stats(*[C.byref(x) for x in v]))
+    return dict(zip(names, (x.value for x in v)))
+
+
 def pipe2_store_depth(k: int, r: int) -> tuple[int, bool]:
     """(store depth, run walk) of the pipelined kernel of a k x r pass."""
     d, run = C.c_int(), C.c_int()

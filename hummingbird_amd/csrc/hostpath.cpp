@@ -57,6 +57,11 @@ struct Piece {
 
 constexpr int kSlots = 3;
 
+// How the host path cut its work, since load (hbec_host_run_stats): staging
+// chunks queued, column pieces cut, record slots the zero-copy runners filled,
+// hash arenas handed to md5_list.  One increment per event, nothing per byte.
+std::atomic<uint64_t> g_ring_chunks{0}, g_ring_pieces{0}, g_zc_record_slots{0}, g_arena_flushes{0};
+
 struct Ring {
     int dev = -1;
     int cus = 0;  // compute units of dev (grid sizing), read once
@@ -224,6 +229,7 @@ struct ArenaCursor {
     }
     int flush() {  // hash the current arena, move to the next free one
         if (recs == 0) return HBEC_OK;
+        g_arena_flushes.fetch_add(1, std::memory_order_relaxed);
         const int a = cur;
         hipStream_t hs = ring->s_md5[a];
         hipError_t e = hipEventRecord(ring->ev_arena_copied[a], producer);
@@ -460,6 +466,7 @@ int zero_copy_run(Ring* ring, const std::vector<ZcStripe>& zs, const std::vector
         e = hipMemcpyAsync(ring->dev_tiles[slot], rec, nt * sizeof(hbec::TileRec), hipMemcpyHostToDevice,
                            ring->s_cmp);
         if (e != hipSuccess) return hip_fail(e, "zero-copy records H2D");
+        g_zc_record_slots.fetch_add(1, std::memory_order_relaxed);
         int rc = hbec::launch_stripe_passes(ring->dev_tiles[slot], nt, in_idx, out_idx, rows, 0, ring->s_cmp,
                                             zero_copy_blocks_per_cu(), false, zero_copy_max_blocks());
         if (rc) return rc;
@@ -503,6 +510,7 @@ int zero_copy_unaligned_run(Ring* ring, const std::vector<ZcStripe>& zs, const s
         e = hipMemcpyAsync(ring->dev_tiles[slot], rec, (nt + edges.size()) * sizeof(hbec::URec), hipMemcpyHostToDevice,
                            ring->s_cmp);
         if (e != hipSuccess) return hip_fail(e, "zero-copy records H2D");
+        g_zc_record_slots.fetch_add(1, std::memory_order_relaxed);
         const hbec::URec* d_rec = reinterpret_cast<const hbec::URec*>(ring->dev_tiles[slot]);
         int rc = hbec::launch_unaligned_passes(d_rec, nt, in_idx, out_idx, rows, 0, ring->s_cmp, zero_copy_max_blocks(),
                                                d_rec + nt, edges.size());
@@ -569,6 +577,7 @@ int zero_copy_md5_run(Ring* ring, const std::vector<ZcStripe>& zs, const std::ve
         e = hipMemcpyAsync(ring->dev_tiles[slot], rec, nt * sizeof(hbec::TileRec), hipMemcpyHostToDevice,
                            ring->s_cmp);
         if (e != hipSuccess) return hip_fail(e, "zero-copy records H2D");
+        g_zc_record_slots.fetch_add(1, std::memory_order_relaxed);
         rc = hbec::launch_stripe_passes(ring->dev_tiles[slot], nt, in_idx, out_idx, rows, 0, ring->s_cmp,
                                         zero_copy_blocks_per_cu(), true, zero_copy_max_blocks());
         if (rc) return rc;
@@ -639,6 +648,7 @@ int zero_copy_unaligned_md5_run(Ring* ring, const std::vector<ZcStripe>& zs, con
         e = hipMemcpyAsync(ring->dev_tiles[slot], rec, (nt + edges.size()) * sizeof(hbec::URec), hipMemcpyHostToDevice,
                            ring->s_cmp);
         if (e != hipSuccess) return hip_fail(e, "zero-copy records H2D");
+        g_zc_record_slots.fetch_add(1, std::memory_order_relaxed);
         const hbec::URec* d_rec = reinterpret_cast<const hbec::URec*>(ring->dev_tiles[slot]);
         rc = hbec::launch_unaligned_passes(d_rec, nt, in_idx, out_idx, rows, 0, ring->s_cmp, zero_copy_max_blocks(),
                                            d_rec + nt, edges.size(), true);
@@ -819,6 +829,7 @@ int host_run_on(Ring* ring, const hbec_stripe* stripes, uint64_t n, const std::v
             out_used += R * p.lpad;
             tiles_used += nt;
             chunks.back().push_back(p);
+            g_ring_pieces.fetch_add(1, std::memory_order_relaxed);
         }
     }
     if (chunks.back().empty()) chunks.pop_back();
@@ -918,6 +929,7 @@ int host_run_on(Ring* ring, const hbec_stripe* stripes, uint64_t n, const std::v
         if (e == hipSuccess) e = hipEventRecord(ring->ev_done[slot], ring->s_d2h);
         if (e != hipSuccess) return hip_fail(e, "host path D2H");
         slot_chunk[slot] = (int64_t)c;
+        g_ring_chunks.fetch_add(1, std::memory_order_relaxed);
     }
     for (size_t i = 0; i < chunks.size() + kSlots; ++i) {  // drain in chunk order
         const int slot = (int)(i % kSlots);
@@ -1248,6 +1260,15 @@ int hbec_encode_host_md5(hbec_codec* codec, const hbec_stripe* stripes, uint64_t
 int hbec_host_md5_stats(uint64_t* zero_copy_calls, uint64_t* ring_calls) {
     if (zero_copy_calls) *zero_copy_calls = g_md5_zc_calls.load(std::memory_order_relaxed);
     if (ring_calls) *ring_calls = g_md5_ring_calls.load(std::memory_order_relaxed);
+    return HBEC_OK;
+}
+
+int hbec_host_run_stats(uint64_t* ring_chunks, uint64_t* ring_pieces, uint64_t* zc_record_slots,
+                        uint64_t* arena_flushes) {
+    if (ring_chunks) *ring_chunks = g_ring_chunks.load(std::memory_order_relaxed);
+    if (ring_pieces) *ring_pieces = g_ring_pieces.load(std::memory_order_relaxed);
+    if (zc_record_slots) *zc_record_slots = g_zc_record_slots.load(std::memory_order_relaxed);
+    if (arena_flushes) *arena_flushes = g_arena_flushes.load(std::memory_order_relaxed);
     return HBEC_OK;
 }
 

@@ -89,6 +89,10 @@ struct TileRec;
 // (one block of 4 waves per CU at most, as the strided kernels).
 // blocks_per_cu > 0 overrides the HBM sweet spot (1 block per CU).
 int stripes_grid(int k, int r, uint64_t n_tiles, int* grid, int blocks_per_cu = 0, int max_blocks = 0);
+// variants of gf_apply_stripes as hbec_stripes_kernel_stats counts them, and
+// the launches of one since load (stripes.hip launch_stripes)
+enum { kSkPlain = 0, kSkSplit, kSkAcc, kSkMirror, kSkMirrorAcc, kSkCount };
+uint64_t stripes_launches(int variant);
 // out (^)= rows x in over tile records, in launches of <= 3 outputs and
 // <= 8 inputs (k > 8: accumulate passes).  sel_k > 0: object-plan bases.
 // mirror: code in place at each record's in_addr and copy every input and

@@ -524,6 +524,10 @@ int hbec::launch_unaligned_passes(const URec* recs, uint64_t n_recs, const std::
     return HBEC_OK;
 }
 
+// test hook (hbec_set_stripes_grid_cap): blocks per gf_apply_stripes launch, so
+// a plan of a few hundred tiles walks the pipelined loop; 0 = no cap
+static std::atomic<int> g_stripes_grid_cap{0};
+
 int hbec::stripes_grid(int k, int r, uint64_t n_tiles, int* grid, int blocks_per_cu, int max_blocks) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -552,6 +556,8 @@ int hbec::stripes_grid(int k, int r, uint64_t n_tiles, int* grid, int blocks_per
     }
     uint64_t cap = (uint64_t)cus * (uint64_t)bpc;
     if (max_blocks > 0) cap = std::min<uint64_t>(cap, (uint64_t)max_blocks);
+    if (const int hook = g_stripes_grid_cap.load(std::memory_order_relaxed); hook > 0)
+        cap = std::min<uint64_t>(cap, (uint64_t)hook);
     *grid = (int)std::max<uint64_t>(1, std::min(want, cap));
     return HBEC_OK;
 }
@@ -1795,6 +1801,24 @@ int hbec_mixed_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls)
         if (!kernel_launches || !per_stripe_calls) return fail(HBEC_ERR_INVALID_ARG, "null argument");
         *kernel_launches = g_mplan_launches.load(std::memory_order_relaxed);
         *per_stripe_calls = g_mplan_per_stripe.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_stripes_kernel_stats(uint64_t* plain, uint64_t* split, uint64_t* accumulate, uint64_t* mirror,
+                              uint64_t* mirror_accumulate) {
+    return hbec::guarded("hbec_stripes_kernel_stats", [&]() -> int {
+        uint64_t* const out[hbec::kSkCount] = {plain, split, accumulate, mirror, mirror_accumulate};
+        for (int i = 0; i < hbec::kSkCount; ++i)
+            if (out[i]) *out[i] = hbec::stripes_launches(i);
+        return HBEC_OK;
+    });
+}
+
+int hbec_set_stripes_grid_cap(int blocks) {
+    return hbec::guarded("hbec_set_stripes_grid_cap", [&]() -> int {
+        if (blocks < 0) return fail(HBEC_ERR_INVALID_ARG, "stripes grid cap: negative");
+        g_stripes_grid_cap.store(blocks, std::memory_order_relaxed);
         return HBEC_OK;
     });
 }

@@ -17,6 +17,7 @@
 #include <atomic>
 
 #include "gf_device.h"
+#include "internal.h"
 #include "kernels.h"
 
 namespace hbec {
@@ -263,12 +264,24 @@ int stripes_tile_bytes(int k) { return stripes_u(k) * 1024; }
 
 bool stripes_supported(int k, int r) { return stripes_kernel(k, r) != nullptr; }
 
+// launches since load by variant (hbec_stripes_kernel_stats): tests prove
+// from them which of the 120 instances coded a plan or a host chunk
+static std::atomic<uint64_t> g_stripes_launches[kSkCount];
+
+uint64_t stripes_launches(int variant) { return g_stripes_launches[variant].load(std::memory_order_relaxed); }
+
 hipError_t launch_stripes(int k, int r, const StripeArgs& a, int grid, hipStream_t stream) {
     const void* fn = stripes_kernel(k, r, a.split != 0, a.accumulate != 0, a.mirror != 0);
     if (!fn) return hipErrorInvalidValue;
     const TileRec* tiles = a.tiles;
     void* args[] = {const_cast<StripeArgs*>(&a), &tiles};
-    return hipLaunchKernel(fn, dim3(grid), dim3(kBlockThreads), args, 0, stream);
+    const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlockThreads), args, 0, stream);
+    if (e == hipSuccess) {
+        const int which = a.mirror ? (a.accumulate ? kSkMirrorAcc : kSkMirror)
+                                   : (a.accumulate ? kSkAcc : (a.split ? kSkSplit : kSkPlain));
+        g_stripes_launches[which].fetch_add(1, std::memory_order_relaxed);
+    }
+    return e;
 }
 
 hipError_t stripes_occupancy(int k, int r, int* blocks_per_cu) {

@@ -734,6 +734,15 @@ int hbec_reconstruct_host_devices(hbec_codec* codec, const hbec_stripe* stripes,
  * that took each way. */
 int hbec_encode_host_md5(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n_stripes, uint8_t* digests);
 int hbec_host_md5_stats(uint64_t* zero_copy_calls, uint64_t* ring_calls);
+/* How the host calls (hbec_encode_host, hbec_reconstruct_host,
+ * hbec_encode_host_md5) cut their work, since load: staging chunks queued;
+ * column pieces cut (a stripe that fits a slot is one piece, a wider one
+ * ceil(S / piece width)); record slots the four zero-copy runners filled and
+ * sent (aligned, unaligned, and their hashing forms); hash arenas handed to
+ * md5_list (non-empty flushes).  One count per event, none per byte or tile.
+ * Any pointer may be NULL; needs no device. */
+int hbec_host_run_stats(uint64_t* ring_chunks, uint64_t* ring_pieces, uint64_t* zc_record_slots,
+                        uint64_t* arena_flushes);
 
 /* Batching driver for concurrent callers (e.g. one cgo call per Stabilize):
  * each call submits ONE host stripe and blocks until it is coded; worker
@@ -782,6 +791,20 @@ int hbec_vec_launch_config(uint64_t* chunk_tiles, int* grid_cap);
  * gf_apply_vec_stream.  hbec_apply_route_stats counts the last four as one.
  * Any pointer may be NULL; needs no device. */
 int hbec_vec_kernel_stats(uint64_t* packed, uint64_t* pipe2, uint64_t* pipe, uint64_t* vec, uint64_t* stream);
+/* Launches since load of the tiled stripes kernel gf_apply_stripes (stripe and
+ * object plans, the host staging ring, pinned stripes coded in place), by
+ * variant: plain (a stripe plan's or the host path's first pass of <= 8
+ * inputs), split (every pass of an object plan), accumulate (later passes of
+ * k > 8), mirror and mirror_accumulate (hbec_encode_host_md5 on pinned
+ * stripes).  Any pointer may be NULL; needs no device. */
+int hbec_stripes_kernel_stats(uint64_t* plain, uint64_t* split, uint64_t* accumulate, uint64_t* mirror,
+                              uint64_t* mirror_accumulate);
+/* Test hook, process-wide: a cap on the grid of gf_apply_stripes in blocks of
+ * 4 waves (0 = none, negative is refused), applied after every other bound, so
+ * a plan of a few hundred tiles walks the kernel's pipelined loop hundreds of
+ * times and its tile count mod 4 decides the stand-in tiles of the last row.
+ * Not for production use. */
+int hbec_set_stripes_grid_cap(int blocks);
 /* Store depth of the pipelined kernel gf_apply_vec_pipe2 for a k x r pass
  * (tiles whose outputs a wave stores in one burst; 1 for every other kernel)
  * and whether its blocks walk runs of consecutive tiles. */

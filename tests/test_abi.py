@@ -34,6 +34,8 @@ def test_library_exports_every_header_symbol():
     assert declared, "no symbols parsed from include/hbec.h"
     assert declared <= exported, sorted(declared - exported)
     assert declared == set(N.SYMBOLS)
+    # the counters and the hook the stripes and host-seam sweeps read
+    assert {"hbec_stripes_kernel_stats", "hbec_set_stripes_grid_cap", "hbec_host_run_stats"} <= declared
 
 
 def test_version_and_strerror():
