@@ -124,8 +124,6 @@ inline bool heal_build(HealStage& h, int k, int m, const std::vector<uint32_t>& 
     return true;
 }
 
-uint32_t heal_plan_tile_bytes();
-
 // Tiles [0, n_tiles) of `tiles`, instance r = m.  For every tile whose entry has
 // an index (not kHealNone) and an examined word: with a named shard j whose
 // word heal_word[index][j] is not 0, the tile of that record runs (outputs

@@ -102,8 +102,6 @@ inline uint8_t loc_pattern_coef(const uint32_t* p, int r, int t, int q) {
     return (uint8_t)(p[kMPatHdr + 5 * (t * r + q)] >> 8);
 }
 
-uint32_t locate_plan_tile_bytes();
-
 // Tiles [0, n_tiles) of `tiles`: every tile whose entry passes the filter
 // (flags == nullptr, or flags[entry] & 1) and whose word has 1..r checked shards
 // (r >= 1: the largest count in the call) is compared, and classified where it

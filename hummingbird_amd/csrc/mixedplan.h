@@ -57,6 +57,8 @@ struct MixedPlanRecs {
     std::vector<uint32_t> other;  // source positions coded one call each
 };
 
+// shard bytes per tile of the list, for every kernel that walks it (Verify,
+// repair, locate and heal too)
 uint32_t mixed_plan_tile_bytes();
 
 // the shapes gf_mixed_plan takes: those of the plan Verify kernels

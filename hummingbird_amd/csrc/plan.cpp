@@ -7,18 +7,9 @@
 // their own records; stripe plans with k > 8 run the tiled kernel in
 // accumulate passes.  Verify of a plan (hbec_verify_plan) is read-only and
 // runs over the same tile records plus per-stripe records of its own
-// (vplan.h, vplan.hip).  Reconstruct with an erasure pattern per stripe
-// (hbec_reconstruct_plan_mixed) runs over per-source-entry records and a tile
-// list of its own, built on first use (mixedplan.h, mixedplan.hip); Verify with
-// a present mask per stripe (hbec_verify_plan_mixed) reads the same records and
-// list (vmixed.h, vmixed.hip), and so does the call that rebuilds and checks in
-// one pass (hbec_repair_plan_mixed; repair.h, repair.hip) and the call that
-// rebuilds the shard locate named (hbec_heal_plan_mixed; heal.h, heal.hip).
-// The ShardHash audit of a plan (hbec_hash_plan_mixed; hashplan.h, hashplan.hip)
-// has records of its own with 64-bit lengths, built on first use likewise, and
-// stages its chain list where those calls stage their words.  The hash of
-// multi-stripe shard files (hbec_hash_plan_files; hashfiles.h, hashfiles.hip)
-// reads the same records and stages its chains and object table there too.
+// (vplan.h, vplan.hip).  The calls with a pattern or a selection per source
+// entry (hbec_reconstruct_plan_mixed and the six after it) are in
+// plan_calls.cpp; they run over per-source-entry records built on first use.
 // A plan whose entries name every shard (hbec_plan_shards, hbec_plan_files;
 // shardplan.h) has those records and lists only, with a row of shard addresses
 // where the others have two bases: every call with a pattern per entry takes it
@@ -37,101 +28,17 @@
 
 #include "../../include/hbec.h"
 #include "gf256.h"
-#include "hashfiles.h"
-#include "hashplan.h"
-#include "heal.h"
 #include "internal.h"
 #include "kernels.h"
-#include "locate.h"
 #include "mixedplan.h"
-#include "repair.h"
+#include "plan_internal.h"
 #include "shardplan.h"
-#include "vmixed.h"
 #include "vplan.h"
 
+using hbec::current_cus;
 using hbec::fail;
 using hbec::hip_fail;
-
-struct hbec_plan {
-    int k = 0, m = 0;
-    int tile_bytes = 0;
-    hbec::TileRec* d_tiles = nullptr;
-    uint64_t n_tiles = 0;
-    std::vector<hbec_stripe> tiled;     // stripes covered by d_tiles
-    std::vector<hbec_stripe> fallback;  // stripes coded one by one
-    // object plans (hbec_plan_objects): data shards and parity shards in
-    // separate regions; tiles carry base A = data, base B = parity
-    bool objects = false;
-    std::vector<hbec_object> obj_tiled, obj_fallback;
-    uint64_t shard_bytes = 0;           // sum of shard_len over all stripes
-    // stripes / objects the tiled kernel cannot take: unaligned-kernel records
-    hbec::URec* d_urecs = nullptr;
-    uint64_t n_urecs = 0;
-    // gf_odd: one edge record per such stripe / object (its guard-band bytes)
-    hbec::URec* d_erecs = nullptr;
-    uint64_t n_erecs = 0;
-    // shards of 2^31 bytes or more (gf_odd positions are 32-bit), or all of
-    // them with HBEC_ODD=0: round-2 gf_apply_unaligned_plan records
-    hbec::URec* d_brecs = nullptr;
-    uint64_t n_brecs = 0;
-    // gf_odd_rec: one record per stripe / object with a main-kernel part,
-    // and the tile lists the record kernels walk (one per tile span)
-    hbec::URec* d_orecs = nullptr;
-    uint32_t* d_lists[hbec::kOddSpans] = {};
-    hbec::OddStripeRecs orecs;
-    std::unique_ptr<hbec::OddRecCache> rec_cache;
-    // Verify (hbec_verify_plan).  Every tile record carries its stripe's
-    // position in the caller's array (TileRec::pad_); the stripes without tile
-    // records, or of a shape gf_verify_tiles does not take, have a VRec and
-    // their {record, tile} list; `vother` are the stripes verified one by one.
-    uint64_t n_src = 0;  // entries of the caller's array (zero-length ones included)
-    hbec::VRec* d_vrecs = nullptr;
-    hbec::VTile* d_vtiles = nullptr;
-    uint32_t* d_vtab = nullptr;  // [k][vp_tab_stride(m)] parity coefficient tables
-    uint64_t n_vrecs = 0, n_vtiles = 0;
-    std::vector<hbec::VOther> vother;
-    // Reconstruct and Verify with a pattern per stripe (hbec_reconstruct_plan_mixed,
-    // hbec_verify_plan_mixed): where
-    // every source entry lives, by its position in the caller's array; the
-    // device records and the static {entry, tile} list are built by the first
-    // such call (mp_mu), so a plan that never makes one pays for neither.
-    std::vector<hbec::MSrc> src;
-    mutable std::mutex mp_mu;
-    mutable bool mp_built = false;
-    mutable hbec::MRec* d_mrecs = nullptr;
-    mutable hbec::MTile* d_mtiles = nullptr;
-    mutable uint64_t n_mtiles = 0;
-    mutable std::vector<uint32_t> mp_other;  // source positions rebuilt one call each
-    // a call's pattern records and per-entry words (device), reused call after call
-    mutable uint32_t* d_mstage = nullptr;
-    mutable size_t mstage_words = 0;
-    mutable hipEvent_t mp_ev = nullptr;  // after the last call's launches, on mp_stream
-    mutable hipStream_t mp_stream = nullptr;
-    // hbec_heal_plan_mixed: the records and tables of the last call's masks, on
-    // the host (heal_mu) and on the device (d_heal, under mp_mu and ordered by
-    // mp_ev like d_mstage).  They depend on (k, m) and the masks alone, and a
-    // sweep heals under the masks it has, call after call: the next call with
-    // the same masks inverts no matrix per mask with one shard left out and
-    // stages one index per source entry, nothing else.
-    mutable std::mutex heal_mu;
-    mutable std::vector<uint32_t> heal_bits;
-    mutable std::shared_ptr<const hbec::HealStage> heal_cache;
-    mutable uint32_t* d_heal = nullptr;
-    mutable size_t heal_dev_words = 0;
-    mutable std::shared_ptr<const hbec::HealStage> heal_on_device;  // what d_heal holds
-    // hbec_hash_plan_mixed: a record per source entry with its length in 64 bits
-    // and the non-empty entries longest first, built by the first such call (mp_mu)
-    mutable bool hash_built = false;
-    mutable hbec::HRec* d_hrecs = nullptr;
-    mutable std::vector<uint32_t> hash_order;
-    // shards plans (hbec_plan_shards, hbec_plan_files): shard j of source entry i
-    // is at rows[i (k + m) + j]; d_rows is the same table on the device and
-    // src[i].a the device address of row i (b = 0).
-    // No tile, unaligned or Verify records: every call runs over src.
-    bool shards = false;
-    std::vector<uint64_t> rows;
-    uint64_t* d_rows = nullptr;
-};
+using hbec::upload;
 
 // The gf_odd_rec records of a plan pass depend only on the plan's stripes and
 // on which shards the pass reads and writes, not on its coefficients: a
@@ -228,28 +135,6 @@ int build_tile_lists(hbec_plan* p, const std::vector<hbec::URec>& orecs) {
     p->orecs.n = orecs.size();
     p->orecs.s_max = s_max;
     return HBEC_OK;
-}
-
-template <class T>
-int upload(const std::vector<T>& recs, T** dst, const char* what) {
-    if (recs.empty()) return HBEC_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), recs.size() * sizeof(T));
-    if (e != hipSuccess) return hip_fail(e, what);
-    e = hipMemcpy(*dst, recs.data(), recs.size() * sizeof(T), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(*dst);
-        *dst = nullptr;
-        return hip_fail(e, what);
-    }
-    return HBEC_OK;
-}
-
-// Where shard `sh` of source entry i of a plan is (the host's copy of the rule
-// the kernels hold: two bases, or the entry's row of a shards plan).
-uint64_t shard_addr(const hbec_plan* p, uint32_t i, int sh) {
-    if (p->shards) return p->rows[(size_t)i * (size_t)(p->k + p->m) + (size_t)sh];
-    const hbec::MSrc& s = p->src[i];
-    return sh < p->k ? s.a + (uint64_t)sh * s.shard_len : s.b + (uint64_t)(sh - p->k) * s.shard_len;
 }
 
 // One pass of a plan over per-stripe records: the records of every stripe in
@@ -351,14 +236,6 @@ int upload_verify(hbec_plan* p, hbec_codec* codec, hbec::VerifyRecs& vr) {
 
 std::atomic<uint64_t> g_vplan_launches{0}, g_vplan_per_stripe{0};
 
-// CU count of the current device
-int current_cus(int* cus) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-    return hbec::device_cus(dev, cus);
-}
-
 // One pass of an unaligned plan: inputs [c0, c0 + K) and outputs [r0, r0 + R)
 // of the index lists with their coefficient tables; sel_k > 0: object records
 // (indices >= sel_k are parity, base b).
@@ -426,6 +303,17 @@ int hbec::verify_other_run(hbec_codec* codec, const VOther& o, uint32_t* d_flags
     for (int r = 0; r < m; ++r) v[(size_t)k + r] = {reinterpret_cast<void*>(o.b + (uint64_t)r * o.shard_len), 0};
     g_vplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
     return hbec_verify_batch(codec, v.data(), 1, o.shard_len, d_flags + o.idx, stream);
+}
+
+int hbec::verify_plan_entry(hbec_codec* codec, const hbec_plan* plan, uint32_t i, uint32_t* d_flags,
+                            hipStream_t stream) {
+    const hbec::MSrc& s = plan->src[i];
+    if (!plan->shards) return verify_other_run(codec, VOther{s.a, s.b, s.shard_len, i}, d_flags, stream);
+    // what verify_other_run does, with the entry's own shard addresses
+    std::vector<hbec_view> v((size_t)plan->k + plan->m);
+    for (int sh = 0; sh < plan->k + plan->m; ++sh) v[sh] = {reinterpret_cast<void*>(shard_addr(plan, i, sh)), 0};
+    g_vplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
+    return hbec_verify_batch(codec, v.data(), 1, s.shard_len, d_flags + i, stream);
 }
 
 // out rows (^)= rows x in over unaligned-kernel records, in passes of <= 4
@@ -634,797 +522,9 @@ int run_plan(const hbec_plan* p, const std::vector<int>& in_idx, const std::vect
                                          false, true);
 }
 
-// ---- reconstruct with a pattern per stripe (hbec_reconstruct_plan_mixed) ----
-
-std::atomic<uint64_t> g_mplan_launches{0}, g_mplan_per_stripe{0};
-// test hook (hbec_set_mixed_plan_chunk_tiles): tiles per gf_mixed_plan launch
-std::atomic<uint64_t> g_mplan_chunk_override{0};
-// per-call staging of at most this many bytes goes through kernel arguments
-// (kPutWordsMax words a launch: 18 launches), more through a copy
-constexpr size_t kMPlanPutBytes = 64 * 1024;
-
-// The device side of a plan's mixed reconstruct, built once.
-int mixed_plan_device(const hbec_plan* p) {
-    std::lock_guard<std::mutex> lk(p->mp_mu);
-    if (p->mp_built) return HBEC_OK;
-    hbec::MixedPlanRecs mr;
-    if (!hbec::mp_build(mr, p->k, p->m, p->src, hbec::mixed_plan_tile_bytes()))
-        return fail(HBEC_ERR_INVALID_ARG, "plan too large (>= 2^31 tiles)");
-    if (!mr.tiles.empty()) {
-        int rc = upload(mr.recs, &p->d_mrecs, "plan mixed records");
-        if (!rc) rc = upload(mr.tiles, &p->d_mtiles, "plan mixed tile list");
-        if (rc) {
-            if (p->d_mrecs) (void)hipFree(p->d_mrecs);
-            p->d_mrecs = nullptr;
-            return rc;
-        }
-    }
-    p->n_mtiles = mr.tiles.size();
-    p->mp_other = std::move(mr.other);
-    p->mp_built = true;
-    return HBEC_OK;
-}
-
-// One distinct pattern of a call, resolved.
-struct PlanPattern {
-    std::vector<int> surv, outs;
-    std::vector<uint8_t> rows;  // outs.size() x k
-    uint64_t uses = 0;          // source entries with this pattern
-    uint32_t rec = 0;           // its pattern record (kernel route)
-};
-
-// The argument checks of a call with a pattern per source entry
-// (hbec_reconstruct_plan_mixed, hbec_verify_plan_mixed), all made before anything
-// is queued; counts the non-empty entries of every pattern.
-int check_plan_patterns(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                        const uint32_t* pattern_of, std::vector<PlanPattern>& pats) {
-    if (!codec || !plan || !patterns || !pattern_of) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
-    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
-    if (n_patterns > 65536) return fail(HBEC_ERR_INVALID_ARG, "more than 65536 patterns");
-    const uint64_t n_src = plan->n_src;
-    if (n_src && !n_patterns) return fail(HBEC_ERR_INVALID_ARG, "stripes but no patterns");
-    pats.assign(n_patterns, PlanPattern());
-    for (uint32_t p = 0; p < n_patterns; ++p) {
-        int n_present = 0;
-        for (int i = 0; i < n; ++i) n_present += patterns[(size_t)p * n + i] ? 1 : 0;
-        if (n_present < k)
-            return fail(HBEC_ERR_TOO_FEW_SHARDS, "too few shards given (pattern " + std::to_string(p) + ")");
-    }
-    for (uint64_t i = 0; i < n_src; ++i) {  // zero-length entries too
-        if (pattern_of[i] >= n_patterns)
-            return fail(HBEC_ERR_INVALID_ARG, "pattern index out of range (stripe " + std::to_string(i) + ")");
-        if (plan->src[i].shard_len) ++pats[pattern_of[i]].uses;
-    }
-    return HBEC_OK;
-}
-
-// After a call's launches: the next call on another stream waits for them.
-int stage_end(const hbec_plan* plan, hipStream_t stream) {
-    plan->mp_stream = stream;
-    const hipError_t e = hipEventRecord(plan->mp_ev, stream);
-    return e == hipSuccess ? HBEC_OK : hip_fail(e, "hipEventRecord (plan mixed staging)");
-}
-
-// A call's staging words (pattern records, then one word per source entry) go
-// to a buffer the plan owns, not to stream-ordered scratch: with a scratch
-// allocation and a copy from pageable memory per call, a call returned only
-// when the one before it had run (4096 stripes 4+2: 0.70 of a call's 0.74 ms
-// on the host, against 0.016 ms for hbec_reconstruct_plan), so back-to-back
-// calls never overlapped.  Up to kMPlanPutBytes the words travel in kernel
-// arguments (launch_put_words).  Calls on one plan, reconstruct and verify
-// alike, take turns under mp_mu from stage_begin to stage_end; a call on
-// another stream than the last waits for that call's event, so the words of one
-// call are never overwritten while its launches may still read them.
-int stage_begin(const hbec_plan* plan, const std::vector<uint32_t>& stage, hipStream_t stream) {
-    hipError_t e = hipSuccess;
-    if (stage.size() > plan->mstage_words) {
-        if (plan->d_mstage) (void)hipFree(plan->d_mstage);  // waits for the work that reads it
-        plan->d_mstage = nullptr;
-        plan->mstage_words = 0;
-        const size_t cap = std::max<size_t>(2 * stage.size(), 4096);
-        e = hipMalloc(reinterpret_cast<void**>(&plan->d_mstage), cap * 4);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc plan mixed staging");
-        plan->mstage_words = cap;
-    }
-    if (!plan->mp_ev) {
-        e = hipEventCreateWithFlags(&plan->mp_ev, hipEventDisableTiming);
-        if (e != hipSuccess) return hip_fail(e, "hipEventCreate (plan mixed staging)");
-    } else if (plan->mp_stream != stream) {
-        e = hipStreamWaitEvent(stream, plan->mp_ev, 0);
-        if (e != hipSuccess) return hip_fail(e, "hipStreamWaitEvent (plan mixed staging)");
-    }
-    e = stage.size() * 4 <= kMPlanPutBytes
-            ? hbec::launch_put_words(plan->d_mstage, stage.data(), stage.size() * 4, stream)
-            : hipMemcpyAsync(plan->d_mstage, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) return HBEC_OK;
-    (void)stage_end(plan, stream);
-    return hip_fail(e, "plan mixed staging");
-}
-
-// The other route of the calls with a pattern per source entry (any k, m, S),
-// one source entry at a time; hbec_reconstruct_plan_mixed, hbec_verify_plan_mixed
-// and hbec_repair_plan_mixed share both.
-// Rebuild: one single-pattern apply of pp's decode rows (pp.outs not empty).
-int reconstruct_other_entry(const hbec_plan* plan, uint32_t i, const PlanPattern& pp, hipStream_t stream) {
-    const int k = plan->k;
-    const hbec::MSrc& s = plan->src[i];
-    auto at = [&](int sh) { return hbec_view{reinterpret_cast<void*>(shard_addr(plan, i, sh)), 0}; };
-    std::vector<hbec_view> vin((size_t)k), vout(pp.outs.size());
-    for (int j = 0; j < k; ++j) vin[j] = at(pp.surv[j]);
-    for (size_t q = 0; q < pp.outs.size(); ++q) vout[q] = at(pp.outs[q]);
-    return hbec::apply_views((int)pp.outs.size(), k, pp.rows.data(), vin.data(), vout.data(), 1, s.shard_len, stream);
-}
-
-// Check (pp.outs: the checked shards): exactly k present, bit 1; all present,
-// the per-stripe Verify; degraded, the checked shards rebuilt from the survivors
-// into scratch and compared with the stored ones.
-int verify_other_entry(hbec_codec* codec, const hbec_plan* plan, uint32_t i, const PlanPattern& pp,
-                       uint32_t* d_flags, int cus, hipStream_t stream) {
-    const int k = plan->k, m = plan->m;
-    const hbec::MSrc& s = plan->src[i];
-    if (pp.outs.empty()) {
-        const hipError_t e = hbec::launch_vm_or(d_flags + i, 2u, stream);
-        return e == hipSuccess ? HBEC_OK : hip_fail(e, "launch gf_vm_or");
-    }
-    if ((int)pp.outs.size() == m) {
-        if (!plan->shards) return hbec::verify_other_run(codec, hbec::VOther{s.a, s.b, s.shard_len, i}, d_flags, stream);
-        // what verify_other_run does, with the entry's own shard addresses
-        std::vector<hbec_view> v((size_t)k + m);
-        for (int sh = 0; sh < k + m; ++sh) v[sh] = {reinterpret_cast<void*>(shard_addr(plan, i, sh)), 0};
-        g_vplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
-        return hbec_verify_batch(codec, v.data(), 1, s.shard_len, d_flags + i, stream);
-    }
-    auto at = [&](int sh) { return shard_addr(plan, i, sh); };
-    void* scratch = nullptr;
-    int rc = hbec::scratch_alloc(pp.outs.size() * (size_t)s.shard_len, stream, &scratch);
-    if (rc) return rc;
-    uint8_t* rebuilt = static_cast<uint8_t*>(scratch);
-    std::vector<hbec_view> vin((size_t)k), vout(pp.outs.size());
-    for (int j = 0; j < k; ++j) vin[j] = hbec_view{reinterpret_cast<void*>(at(pp.surv[j])), 0};
-    for (size_t q = 0; q < pp.outs.size(); ++q) vout[q] = hbec_view{rebuilt + q * (size_t)s.shard_len, 0};
-    rc = hbec::apply_views((int)pp.outs.size(), k, pp.rows.data(), vin.data(), vout.data(), 1, s.shard_len, stream);
-    hipError_t e = hipSuccess;
-    for (size_t q = 0; q < pp.outs.size() && !rc && e == hipSuccess; ++q)
-        e = hbec::launch_vm_compare(rebuilt + q * (size_t)s.shard_len, reinterpret_cast<const void*>(at(pp.outs[q])),
-                                    s.shard_len, d_flags + i, cus, stream);
-    hbec::scratch_free(scratch, stream);
-    if (rc) return rc;
-    return e == hipSuccess ? HBEC_OK : hip_fail(e, "launch gf_vm_compare");
-}
-
-int reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                           const uint32_t* pattern_of, bool data_only, hipStream_t stream) {
-    std::vector<PlanPattern> pats;
-    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
-    if (rc) return rc;
-    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
-    const uint64_t n_src = plan->n_src;
-    std::vector<uint8_t> mask((size_t)n);
-    bool work = false;
-    for (uint32_t p = 0; p < n_patterns; ++p) {
-        PlanPattern& pp = pats[p];
-        if (!pp.uses) continue;
-        int n_present = 0, data_present = 0;
-        for (int i = 0; i < n; ++i) {
-            mask[i] = patterns[(size_t)p * n + i] ? 1 : 0;
-            n_present += mask[i];
-            if (i < k) data_present += mask[i];
-        }
-        if (n_present == n || (data_only && data_present == k)) continue;  // nothing to rebuild
-        pp.surv.resize(k);
-        pp.outs.resize(n);
-        pp.rows.resize((size_t)n * k);
-        int n_out = 0;
-        int rc = hbec_decode_rows(codec, mask.data(), data_only ? 1 : 0, pp.surv.data(), pp.outs.data(), &n_out,
-                                  pp.rows.data());
-        if (rc) return rc;
-        pp.outs.resize(n_out);
-        pp.rows.resize((size_t)n_out * k);
-        work = work || n_out > 0;
-    }
-    if (!work) return HBEC_OK;
-    rc = mixed_plan_device(plan);
-    if (rc) return rc;
-
-    if (plan->n_mtiles > 0) {
-        // per call: the records of the patterns in use and one word per source
-        // entry, in one buffer, to stream-ordered scratch
-        std::vector<uint32_t> stage;
-        for (PlanPattern& pp : pats) {
-            if (!pp.uses || pp.outs.empty()) continue;
-            pp.rec = hbec::mp_pattern(stage, k, pp.surv.data(), pp.outs.data(), (int)pp.outs.size(), pp.rows.data());
-        }
-        const size_t rec_words = stage.size();
-        stage.resize(rec_words + (size_t)n_src);
-        uint32_t* words = stage.data() + rec_words;
-        bool has_r[hbec::kMaxR + 1] = {};
-        for (uint64_t i = 0; i < n_src; ++i) {
-            const PlanPattern& pp = pats[pattern_of[i]];
-            const uint64_t S = plan->src[i].shard_len;
-            const bool kernel = S > 0 && hbec::pos32_shard(S) && !pp.outs.empty();  // mp_build's route
-            words[i] = kernel ? ((uint32_t)pp.outs.size() << hbec::kMPatShift) | pp.rec : 0u;
-            if (kernel) has_r[pp.outs.size()] = true;
-        }
-        int cus = 0;
-        rc = current_cus(&cus);
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(plan->mp_mu);
-        rc = stage_begin(plan, stage, stream);
-        if (rc) return rc;
-        const uint32_t* d_pats = plan->d_mstage;
-        const uint32_t* d_words = d_pats + rec_words;
-        hipError_t e = hipSuccess;
-        const uint64_t hook = g_mplan_chunk_override.load(std::memory_order_relaxed);
-        const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
-        // one launch per chunk of the list, of the instance for the largest
-        // output count in use: it codes every tile with something to rebuild
-        int rmax = 0;
-        for (int r = 1; r <= hbec::kMaxR; ++r)
-            if (has_r[r]) rmax = r;
-        for (uint64_t t0 = 0; rmax > 0 && t0 < plan->n_mtiles && e == hipSuccess; t0 += chunk) {
-            const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
-            g_mplan_launches.fetch_add(1, std::memory_order_relaxed);
-            e = hbec::launch_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats, cus, stream,
-                                        plan->shards);
-        }
-        rc = stage_end(plan, stream);
-        if (e != hipSuccess) return hip_fail(e, "launch gf_mixed_plan");
-        if (rc) return rc;
-    }
-    // the other route: one single-pattern apply per stripe (any k, m, S)
-    for (uint32_t i : plan->mp_other) {
-        const PlanPattern& pp = pats[pattern_of[i]];
-        if (pp.outs.empty()) continue;
-        g_mplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
-        rc = reconstruct_other_entry(plan, i, pp, stream);
-        if (rc) return rc;
-    }
-    return HBEC_OK;
-}
-
-// ---- Verify with a present mask per stripe (hbec_verify_plan_mixed) ----
-
-std::atomic<uint64_t> g_vmplan_launches{0}, g_vmplan_per_stripe{0};
-// test hook (hbec_set_verify_mixed_plan_chunk_tiles): tiles per gf_verify_mixed_plan launch
-std::atomic<uint64_t> g_vmplan_chunk_override{0};
-
-int verify_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                      const uint32_t* pattern_of, uint32_t* d_flags, hipStream_t stream) {
-    std::vector<PlanPattern> pats;  // outs: the checked shards
-    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
-    if (rc) return rc;
-    if (!d_flags && plan->n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
-    const uint64_t n_src = plan->n_src;
-    std::vector<uint8_t> mask((size_t)n);
-    bool used = false;
-    for (uint32_t p = 0; p < n_patterns; ++p) {
-        PlanPattern& pp = pats[p];
-        if (!pp.uses) continue;
-        used = true;
-        for (int i = 0; i < n; ++i) mask[i] = patterns[(size_t)p * n + i] ? 1 : 0;
-        pp.surv.resize(k);
-        pp.outs.resize(std::max(1, m));
-        pp.rows.resize((size_t)std::max(1, m) * k);
-        int n_checked = 0;
-        rc = hbec_check_rows(codec, mask.data(), pp.surv.data(), pp.outs.data(), &n_checked, pp.rows.data());
-        if (rc) return rc;
-        pp.outs.resize(n_checked);
-        pp.rows.resize((size_t)n_checked * k);
-    }
-    if (!used) return HBEC_OK;  // zero-length entries only
-    rc = mixed_plan_device(plan);
-    if (rc) return rc;
-    int cus = 0;
-    rc = current_cus(&cus);
-    if (rc) return rc;
-
-    if (plan->n_mtiles > 0) {
-        // per call, as reconstruct_plan_mixed: the records of the masks with
-        // something to check and one word per source entry, in one buffer
-        std::vector<uint32_t> stage;
-        for (PlanPattern& pp : pats) {
-            if (!pp.uses || pp.outs.empty()) continue;
-            pp.rec = hbec::vm_pattern(stage, k, pp.surv.data(), pp.outs.data(), (int)pp.outs.size(), pp.rows.data());
-        }
-        const size_t rec_words = stage.size();
-        stage.resize(rec_words + (size_t)n_src);
-        uint32_t* words = stage.data() + rec_words;
-        int rmax = 1;  // exactly-k entries alone: any instance sets their bit
-        for (uint64_t i = 0; i < n_src; ++i) {
-            const PlanPattern& pp = pats[pattern_of[i]];
-            const bool kernel = hbec::vm_route(k, m, plan->src[i].shard_len) == hbec::kVmKernel;
-            words[i] = kernel ? hbec::vm_word((int)pp.outs.size(), pp.rec) : 0u;
-            if (kernel) rmax = std::max(rmax, (int)pp.outs.size());
-        }
-        std::lock_guard<std::mutex> lk(plan->mp_mu);
-        rc = stage_begin(plan, stage, stream);
-        if (rc) return rc;
-        const uint32_t* d_pats = plan->d_mstage;
-        const uint32_t* d_words = d_pats + rec_words;
-        hipError_t e = hipSuccess;
-        const uint64_t hook = g_vmplan_chunk_override.load(std::memory_order_relaxed);
-        const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
-        // one launch per chunk of the list, of the instance for the largest count
-        // of checked shards in use
-        for (uint64_t t0 = 0; t0 < plan->n_mtiles && e == hipSuccess; t0 += chunk) {
-            const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
-            g_vmplan_launches.fetch_add(1, std::memory_order_relaxed);
-            e = hbec::launch_verify_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats,
-                                               d_flags, cus, stream, plan->shards);
-        }
-        rc = stage_end(plan, stream);
-        if (e != hipSuccess) return hip_fail(e, "launch gf_verify_mixed_plan");
-        if (rc) return rc;
-    }
-    // the other route, one stripe at a time (any k, m, S)
-    for (uint32_t i : plan->mp_other) {
-        g_vmplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
-        rc = verify_other_entry(codec, plan, i, pats[pattern_of[i]], d_flags, cus, stream);
-        if (rc) return rc;
-    }
-    return HBEC_OK;
-}
-
-// ---- rebuild the missing shards and check the surplus ones (hbec_repair_plan_mixed) ----
-
-std::atomic<uint64_t> g_rplan_launches{0}, g_rplan_per_stripe{0};
-// test hook (hbec_set_repair_plan_chunk_tiles): tiles per gf_repair_mixed_plan launch
-std::atomic<uint64_t> g_rplan_chunk_override{0};
-
-int repair_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                      const uint32_t* pattern_of, bool data_only, uint32_t* d_flags, hipStream_t stream) {
-    std::vector<PlanPattern> outp;  // outs: the shards to rebuild (reconstruct_plan_mixed's)
-    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, outp);
-    if (rc) return rc;
-    if (!d_flags && plan->n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
-    const uint64_t n_src = plan->n_src;
-    std::vector<PlanPattern> chkp(n_patterns);  // outs: the checked shards (verify_plan_mixed's)
-    std::vector<uint8_t> mask((size_t)n);
-    bool used = false;
-    for (uint32_t p = 0; p < n_patterns; ++p) {
-        PlanPattern &po = outp[p], &pc = chkp[p];
-        if (!po.uses) continue;
-        used = true;
-        int n_present = 0, data_present = 0;
-        for (int i = 0; i < n; ++i) {
-            mask[i] = patterns[(size_t)p * n + i] ? 1 : 0;
-            n_present += mask[i];
-            if (i < k) data_present += mask[i];
-        }
-        pc.surv.resize(k);
-        pc.outs.resize(std::max(1, m));
-        pc.rows.resize((size_t)std::max(1, m) * k);
-        int n_checked = 0;
-        rc = hbec_check_rows(codec, mask.data(), pc.surv.data(), pc.outs.data(), &n_checked, pc.rows.data());
-        if (rc) return rc;
-        pc.outs.resize(n_checked);
-        pc.rows.resize((size_t)n_checked * k);
-        if (n_present == n || (data_only && data_present == k)) continue;  // nothing to rebuild
-        po.surv.resize(k);
-        po.outs.resize(n);
-        po.rows.resize((size_t)n * k);
-        int n_out = 0;
-        rc = hbec_decode_rows(codec, mask.data(), data_only ? 1 : 0, po.surv.data(), po.outs.data(), &n_out,
-                              po.rows.data());
-        if (rc) return rc;
-        po.outs.resize(n_out);
-        po.rows.resize((size_t)n_out * k);
-    }
-    if (!used) return HBEC_OK;  // zero-length entries only
-    rc = mixed_plan_device(plan);
-    if (rc) return rc;
-    int cus = 0;
-    rc = current_cus(&cus);
-    if (rc) return rc;
-
-    if (plan->n_mtiles > 0) {
-        // per call, as verify_plan_mixed: the records of the masks with a shard
-        // to rebuild or to check and one word per source entry, in one buffer
-        std::vector<uint32_t> stage;
-        for (uint32_t p = 0; p < n_patterns; ++p) {
-            PlanPattern &po = outp[p], &pc = chkp[p];
-            if (!po.uses || po.outs.size() + pc.outs.size() == 0) continue;
-            po.rec = hbec::rp_pattern(stage, k, pc.surv.data(), po.outs.data(), (int)po.outs.size(), po.rows.data(),
-                                      pc.outs.data(), (int)pc.outs.size(), pc.rows.data());
-        }
-        const size_t rec_words = stage.size();
-        stage.resize(rec_words + (size_t)n_src);
-        uint32_t* words = stage.data() + rec_words;
-        int rmax = 1;  // exactly-k entries with nothing to rebuild alone: any instance sets their bit
-        for (uint64_t i = 0; i < n_src; ++i) {
-            const PlanPattern &po = outp[pattern_of[i]], &pc = chkp[pattern_of[i]];
-            const bool kernel = hbec::rp_route(k, m, plan->src[i].shard_len) == hbec::kVmKernel;
-            words[i] = kernel ? hbec::rp_word((int)po.outs.size(), (int)pc.outs.size(), po.rec) : 0u;
-            if (kernel) rmax = std::max(rmax, (int)(po.outs.size() + pc.outs.size()));
-        }
-        std::lock_guard<std::mutex> lk(plan->mp_mu);
-        rc = stage_begin(plan, stage, stream);
-        if (rc) return rc;
-        const uint32_t* d_pats = plan->d_mstage;
-        const uint32_t* d_words = d_pats + rec_words;
-        hipError_t e = hipSuccess;
-        const uint64_t hook = g_rplan_chunk_override.load(std::memory_order_relaxed);
-        const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
-        // one launch per chunk of the list, of the instance for the largest count
-        // of rows (outputs and checked shards together) in use
-        for (uint64_t t0 = 0; t0 < plan->n_mtiles && e == hipSuccess; t0 += chunk) {
-            const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
-            g_rplan_launches.fetch_add(1, std::memory_order_relaxed);
-            e = hbec::launch_repair_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats,
-                                               d_flags, cus, stream, plan->shards);
-        }
-        rc = stage_end(plan, stream);
-        if (e != hipSuccess) return hip_fail(e, "launch gf_repair_mixed_plan");
-        if (rc) return rc;
-    }
-    // the other route, one stripe at a time (any k, m, S): what verify_plan_mixed
-    // does with the entry, then what reconstruct_plan_mixed does with it
-    for (uint32_t i : plan->mp_other) {
-        g_rplan_per_stripe.fetch_add(1, std::memory_order_relaxed);
-        rc = verify_other_entry(codec, plan, i, chkp[pattern_of[i]], d_flags, cus, stream);
-        if (rc) return rc;
-        const PlanPattern& po = outp[pattern_of[i]];
-        if (po.outs.empty()) continue;
-        rc = reconstruct_other_entry(plan, i, po, stream);
-        if (rc) return rc;
-    }
-    return HBEC_OK;
-}
-
-// ---- the corrupt shard of every inconsistent stripe (hbec_locate_plan_mixed) ----
-
-std::atomic<uint64_t> g_locplan_launches{0}, g_locplan_skipped{0};
-// test hook (hbec_set_locate_plan_chunk_tiles): tiles per gf_locate_mixed_plan launch
-std::atomic<uint64_t> g_locplan_chunk_override{0};
-
-int locate_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                      const uint32_t* pattern_of, const uint32_t* d_flags, uint32_t* d_where, hipStream_t stream) {
-    std::vector<PlanPattern> pats;  // outs: the checked shards
-    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
-    if (rc) return rc;
-    if (!d_where && plan->n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-    if (d_where && d_where == d_flags) return fail(HBEC_ERR_INVALID_ARG, "d_where aliases d_flags");
-    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
-    const uint64_t n_src = plan->n_src;
-    std::vector<uint8_t> mask((size_t)n);
-    bool used = false;
-    for (uint32_t p = 0; p < n_patterns; ++p) {
-        PlanPattern& pp = pats[p];
-        if (!pp.uses) continue;
-        used = true;
-        for (int i = 0; i < n; ++i) mask[i] = patterns[(size_t)p * n + i] ? 1 : 0;
-        pp.surv.resize(k);
-        pp.outs.resize(std::max(1, m));
-        pp.rows.resize((size_t)std::max(1, m) * k);
-        int n_checked = 0;
-        rc = hbec_check_rows(codec, mask.data(), pp.surv.data(), pp.outs.data(), &n_checked, pp.rows.data());
-        if (rc) return rc;
-        pp.outs.resize(n_checked);
-        pp.rows.resize((size_t)n_checked * k);
-    }
-    if (!used) return HBEC_OK;  // zero-length entries only
-    rc = mixed_plan_device(plan);
-    if (rc) return rc;
-
-    if (plan->n_mtiles > 0) {
-        // per call, as verify_plan_mixed: the records of the masks with something
-        // to check and one word per source entry, in one buffer
-        std::vector<uint32_t> stage;
-        for (PlanPattern& pp : pats) {
-            if (!pp.uses || pp.outs.empty()) continue;
-            pp.rec = hbec::loc_pattern(stage, k, pp.surv.data(), pp.outs.data(), (int)pp.outs.size(), pp.rows.data());
-        }
-        const size_t rec_words = stage.size();
-        stage.resize(rec_words + (size_t)n_src);
-        uint32_t* words = stage.data() + rec_words;
-        int rmax = 1;  // exactly-k entries alone: any instance sets their bit
-        for (uint64_t i = 0; i < n_src; ++i) {
-            const PlanPattern& pp = pats[pattern_of[i]];
-            const bool kernel = hbec::loc_route(k, m, plan->src[i].shard_len) == hbec::kVmKernel;
-            words[i] = kernel ? hbec::vm_word((int)pp.outs.size(), pp.rec) : 0u;
-            if (kernel) rmax = std::max(rmax, (int)pp.outs.size());
-        }
-        int cus = 0;
-        rc = current_cus(&cus);
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(plan->mp_mu);
-        rc = stage_begin(plan, stage, stream);
-        if (rc) return rc;
-        const uint32_t* d_pats = plan->d_mstage;
-        const uint32_t* d_words = d_pats + rec_words;
-        hipError_t e = hipSuccess;
-        const uint64_t hook = g_locplan_chunk_override.load(std::memory_order_relaxed);
-        const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
-        for (uint64_t t0 = 0; t0 < plan->n_mtiles && e == hipSuccess; t0 += chunk) {
-            const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
-            g_locplan_launches.fetch_add(1, std::memory_order_relaxed);
-            e = hbec::launch_locate_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_words, d_pats,
-                                               d_flags, d_where, cus, stream, plan->shards);
-        }
-        rc = stage_end(plan, stream);
-        if (e != hipSuccess) return hip_fail(e, "launch gf_locate_mixed_plan");
-        if (rc) return rc;
-    }
-    // the other route is not examined: said in the entry's word, and counted
-    for (uint32_t i : plan->mp_other) {
-        g_locplan_skipped.fetch_add(1, std::memory_order_relaxed);
-        const hipError_t e = hbec::launch_vm_or(d_where + i, hbec::kLocSkipped, stream);
-        if (e != hipSuccess) return hip_fail(e, "launch gf_vm_or");
-    }
-    return HBEC_OK;
-}
-
-// ---- rebuild the shard locate named (hbec_heal_plan_mixed) ----
-
-std::atomic<uint64_t> g_healplan_launches{0}, g_healplan_skipped{0};
-// test hook (hbec_set_heal_plan_chunk_tiles): tiles per gf_heal_mixed_plan launch
-std::atomic<uint64_t> g_healplan_chunk_override{0};
-
-int heal_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                    const uint32_t* pattern_of, const uint32_t* d_where, uint32_t* d_flags, hipStream_t stream) {
-    std::vector<PlanPattern> pats;
-    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
-    if (rc) return rc;
-    if ((!d_where || !d_flags) && plan->n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-    if (d_where && d_where == d_flags) return fail(HBEC_ERR_INVALID_ARG, "d_where aliases d_flags");
-    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
-    const uint64_t n_src = plan->n_src;
-    // the masks kernel-route entries use, in order of first use: their rows of the tables
-    std::vector<uint32_t> row_of(n_patterns, hbec::kHealNone), bits;
-    for (uint64_t i = 0; i < n_src; ++i) {
-        if (hbec::heal_route(k, m, plan->src[i].shard_len) != hbec::kVmKernel) continue;
-        uint32_t& row = row_of[pattern_of[i]];
-        if (row != hbec::kHealNone) continue;
-        row = (uint32_t)bits.size();
-        bits.push_back(hbec::heal_mask_bits(n, patterns + (size_t)pattern_of[i] * n));
-    }
-    std::shared_ptr<const hbec::HealStage> hs;
-    if (!bits.empty()) {
-        {
-            std::lock_guard<std::mutex> lk(plan->heal_mu);
-            if (plan->heal_cache && plan->heal_bits == bits) hs = plan->heal_cache;
-        }
-        if (!hs) {
-            auto built = std::make_shared<hbec::HealStage>();
-            int err = HBEC_OK;
-            const bool ok = hbec::heal_build(
-                *built, k, m, bits,
-                [&](const uint8_t* mask, int* surv, int* outs, int* n_out, uint8_t* orows, int* chk, int* n_chk,
-                    uint8_t* crows) {
-                    err = hbec_decode_rows(codec, mask, 0, surv, outs, n_out, orows);
-                    if (!err) err = hbec_check_rows(codec, mask, surv, chk, n_chk, crows);
-                    return err == HBEC_OK;
-                });
-            if (built->overflow)
-                return fail(HBEC_ERR_INVALID_ARG,
-                            "pattern records of the masks with one shard left out exceed 64 MiB");
-            if (!ok) return err ? err : fail(HBEC_ERR_INVALID_ARG, "heal records");
-            built->rec_of.clear();  // only the build needs it
-            hs = built;
-            std::lock_guard<std::mutex> lk(plan->heal_mu);
-            plan->heal_bits = bits;
-            plan->heal_cache = hs;
-        }
-    }
-    rc = mixed_plan_device(plan);
-    if (rc) return rc;
-
-    if (plan->n_mtiles > 0 && !bits.empty()) {
-        const hbec::HealStage& h = *hs;
-        std::vector<uint32_t> index((size_t)n_src);
-        for (uint64_t i = 0; i < n_src; ++i)
-            index[i] = hbec::heal_route(k, m, plan->src[i].shard_len) == hbec::kVmKernel ? row_of[pattern_of[i]]
-                                                                                         : hbec::kHealNone;
-        int cus = 0;
-        rc = current_cus(&cus);
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(plan->mp_mu);
-        rc = stage_begin(plan, index, stream);
-        if (rc) return rc;
-        hipError_t e = hipSuccess;
-        if (plan->heal_on_device != hs) {
-            // other masks than the last call's: their records and tables replace those.  This
-            // stream has waited for the last call's launches (stage_begin), so nothing reads them.
-            plan->heal_on_device.reset();
-            if (h.stage.size() > plan->heal_dev_words) {
-                if (plan->d_heal) (void)hipFree(plan->d_heal);
-                plan->d_heal = nullptr;
-                plan->heal_dev_words = 0;
-                const size_t cap = std::max<size_t>(2 * h.stage.size(), 4096);
-                e = hipMalloc(reinterpret_cast<void**>(&plan->d_heal), cap * 4);
-                if (e == hipSuccess) plan->heal_dev_words = cap;
-            }
-            if (e == hipSuccess)
-                e = h.stage.size() * 4 <= kMPlanPutBytes
-                        ? hbec::launch_put_words(plan->d_heal, h.stage.data(), h.stage.size() * 4, stream)
-                        : hipMemcpyAsync(plan->d_heal, h.stage.data(), h.stage.size() * 4, hipMemcpyHostToDevice,
-                                         stream);
-            if (e != hipSuccess) {
-                (void)stage_end(plan, stream);
-                return hip_fail(e, "plan heal records");
-            }
-            plan->heal_on_device = hs;
-        }
-        const uint32_t* d_pats = plan->d_heal;
-        const uint32_t* d_index = plan->d_mstage;
-        const uint64_t hook = g_healplan_chunk_override.load(std::memory_order_relaxed);
-        const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
-        // one launch per chunk of the list; every mask with one shard left out has m rows
-        for (uint64_t t0 = 0; t0 < plan->n_mtiles && e == hipSuccess; t0 += chunk) {
-            const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, plan->n_mtiles - t0);
-            g_healplan_launches.fetch_add(1, std::memory_order_relaxed);
-            e = hbec::launch_heal_mixed_plan(k, std::max(1, m), plan->d_mrecs, plan->d_mtiles + t0, nt, d_index,
-                                             d_pats + h.words_at, d_pats + h.present_at, d_pats, d_where, d_flags,
-                                             cus, stream, plan->shards);
-        }
-        rc = stage_end(plan, stream);
-        if (e != hipSuccess) return hip_fail(e, "launch gf_heal_mixed_plan");
-        if (rc) return rc;
-    }
-    // the other route is never healed (locate gave it kLocSkipped): counted
-    g_healplan_skipped.fetch_add(plan->mp_other.size(), std::memory_order_relaxed);
-    return HBEC_OK;
-}
-
-// ---- the ShardHash of a plan's shards against the stored ones (hbec_hash_plan_mixed) ----
-
-std::atomic<uint64_t> g_hashplan_launches{0}, g_hashplan_chains{0};
-
-// The device side of a plan's hash call, built once: a record per source entry
-// and the order its chains are listed in.
-int hash_plan_device(const hbec_plan* p) {
-    std::lock_guard<std::mutex> lk(p->mp_mu);
-    if (p->hash_built) return HBEC_OK;
-    std::vector<hbec::HRec> recs(p->src.size());
-    for (size_t i = 0; i < p->src.size(); ++i) {
-        const hbec::MSrc& s = p->src[i];
-        recs[i] = hbec::HRec{s.a, s.b, s.shard_len, (uint32_t)hbec::loc_route(p->k, p->m, s.shard_len), 0u};
-    }
-    int rc = upload(recs, &p->d_hrecs, "plan hash records");
-    if (rc) return rc;
-    hbec::hash_order(p->src, p->hash_order);
-    p->hash_built = true;
-    return HBEC_OK;
-}
-
-int hash_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* select, uint32_t n_select,
-                    const uint32_t* select_of, const uint32_t* d_filter, uint32_t filter_bits,
-                    const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad, uint32_t* d_where,
-                    hipStream_t stream) {
-    if (!codec || !plan) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
-    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
-    if (n_select > 65536) return fail(HBEC_ERR_INVALID_ARG, "more than 65536 selection rows");
-    // what the given pointers say about each other holds for any plan
-    if (d_where && !d_bad) return fail(HBEC_ERR_INVALID_ARG, "d_where needs d_bad");
-    if (d_expected && !d_bad) return fail(HBEC_ERR_INVALID_ARG, "d_expected needs d_bad");
-    if (d_expected && n > 32) return fail(HBEC_ERR_INVALID_ARG, "d_expected needs k + m <= 32 (one bit per shard)");
-    if ((d_bad && (d_bad == d_where || d_bad == d_filter)) || (d_where && d_where == d_filter))
-        return fail(HBEC_ERR_INVALID_ARG, "d_bad, d_where and d_filter must be distinct");
-    if ((reinterpret_cast<uintptr_t>(d_digests) | reinterpret_cast<uintptr_t>(d_expected)) & 3u)
-        return fail(HBEC_ERR_INVALID_ARG, "digest buffer not 4-byte aligned");
-    const uint64_t n_src = plan->n_src;
-    if (n_src == 0) return HBEC_OK;
-    if (!select || !select_of) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-    if (!n_select) return fail(HBEC_ERR_INVALID_ARG, "stripes but no selection rows");
-    if (!d_digests && !d_expected) return fail(HBEC_ERR_INVALID_ARG, "neither d_digests nor d_expected given");
-    bool any = false;
-    for (uint64_t i = 0; i < n_src; ++i) {  // zero-length entries too
-        if (select_of[i] >= n_select)
-            return fail(HBEC_ERR_INVALID_ARG, "selection index out of range (stripe " + std::to_string(i) + ")");
-        any = any || plan->src[i].shard_len;
-    }
-    if (!any) return HBEC_OK;  // zero-length entries only
-    int rc = hash_plan_device(plan);
-    if (rc) return rc;
-    // per call: the chain list, then (for d_where) every entry's selected-shard bits
-    std::vector<hbec::HChain> chains;
-    hbec::hash_chains(plan->hash_order, n, select, n_select, select_of, chains);
-    if (chains.empty()) return HBEC_OK;
-    if (chains.size() / 64 >= (1ull << 31)) return fail(HBEC_ERR_INVALID_ARG, "call too large (>= 2^37 chains)");
-    const size_t chain_words = chains.size() * (sizeof(hbec::HChain) / 4);
-    std::vector<uint32_t> stage(chain_words + (d_where ? (size_t)n_src : 0));
-    std::memcpy(stage.data(), chains.data(), chain_words * 4);
-    if (d_where) {
-        std::vector<uint32_t> bits(n_select);
-        for (uint32_t p = 0; p < n_select; ++p) bits[p] = hbec::hash_select_bits(n, select + (size_t)p * n);
-        for (uint64_t i = 0; i < n_src; ++i) stage[chain_words + i] = bits[select_of[i]];
-    }
-    std::lock_guard<std::mutex> lk(plan->mp_mu);
-    rc = stage_begin(plan, stage, stream);
-    if (rc) return rc;
-    const hbec::HChain* d_chains = reinterpret_cast<const hbec::HChain*>(plan->d_mstage);
-    g_hashplan_launches.fetch_add(1, std::memory_order_relaxed);
-    g_hashplan_chains.fetch_add(chains.size(), std::memory_order_relaxed);
-    hipError_t e = hbec::launch_md5_plan(plan->d_hrecs, d_chains, chains.size(), k, n, d_filter, filter_bits,
-                                         d_expected, d_digests, d_expected ? d_bad : nullptr, stream, plan->shards);
-    if (e == hipSuccess && d_where) {
-        g_hashplan_launches.fetch_add(1, std::memory_order_relaxed);
-        e = hbec::launch_hash_where(plan->d_hrecs, (uint32_t)n_src, plan->d_mstage + chain_words, d_filter,
-                                    filter_bits, d_bad, d_where, stream);
-    }
-    rc = stage_end(plan, stream);
-    if (e != hipSuccess) return hip_fail(e, "launch md5_plan");
-    return rc;
-}
-
-// ---- the ShardHash of multi-stripe shard files on a plan (hbec_hash_plan_files) ----
-
-std::atomic<uint64_t> g_hashfiles_launches{0}, g_hashfiles_chains{0}, g_hashfiles_segments{0};
-
-int hash_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
-                    const uint8_t* select, uint32_t n_select, const uint32_t* select_of, const uint32_t* d_filter,
-                    uint32_t filter_bits, const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad,
-                    uint32_t* d_where, hipStream_t stream) {
-    if (!codec || !plan) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
-    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
-    if (n_select > 65536) return fail(HBEC_ERR_INVALID_ARG, "more than 65536 selection rows");
-    // what the given pointers say about each other holds for any plan, as in hash_plan_mixed
-    if (d_where && !d_bad) return fail(HBEC_ERR_INVALID_ARG, "d_where needs d_bad");
-    if (d_expected && !d_bad) return fail(HBEC_ERR_INVALID_ARG, "d_expected needs d_bad");
-    if (d_expected && n > 32) return fail(HBEC_ERR_INVALID_ARG, "d_expected needs k + m <= 32 (one bit per shard)");
-    if ((d_bad && (d_bad == d_where || d_bad == d_filter)) || (d_where && d_where == d_filter))
-        return fail(HBEC_ERR_INVALID_ARG, "d_bad, d_where and d_filter must be distinct");
-    if ((reinterpret_cast<uintptr_t>(d_digests) | reinterpret_cast<uintptr_t>(d_expected)) & 3u)
-        return fail(HBEC_ERR_INVALID_ARG, "digest buffer not 4-byte aligned");
-    const uint64_t n_src = plan->n_src;
-    if (n_src == 0) return HBEC_OK;
-    if (const char* why = hbec::files_check_objects(object_start, n_objects, n_src))
-        return fail(HBEC_ERR_INVALID_ARG, why);
-    if (!select || !select_of) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-    if (!d_digests && !d_expected) return fail(HBEC_ERR_INVALID_ARG, "neither d_digests nor d_expected given");
-    for (uint32_t g = 0; g < n_objects; ++g)  // empty objects too
-        if (select_of[g] >= n_select)
-            return fail(HBEC_ERR_INVALID_ARG, "selection index out of range (object " + std::to_string(g) + ")");
-    // per call: the chain list and the object table, then (for d_where) every entry's object
-    // and every object's selected-shard bits
-    std::vector<hbec::FChain> chains;
-    const uint64_t segments = hbec::files_chains(plan->src, object_start, n_objects, n, select, n_select, select_of,
-                                                 chains);
-    if (chains.empty()) return HBEC_OK;  // zero-length entries only, or nothing selected
-    if (chains.size() / 64 >= (1ull << 31)) return fail(HBEC_ERR_INVALID_ARG, "call too large (>= 2^37 chains)");
-    int rc = hash_plan_device(plan);
-    if (rc) return rc;
-    const size_t chain_words = chains.size() * (sizeof(hbec::FChain) / 4);
-    const size_t objects_at = chain_words, of_at = objects_at + n_objects + 1, sel_at = of_at + (size_t)n_src;
-    std::vector<uint32_t> stage(d_where ? sel_at + n_objects : of_at);
-    std::memcpy(stage.data(), chains.data(), chain_words * 4);
-    std::memcpy(stage.data() + objects_at, object_start, ((size_t)n_objects + 1) * 4);
-    if (d_where) {
-        std::vector<uint32_t> object_of;
-        hbec::files_entry_objects(object_start, n_objects, object_of);
-        std::memcpy(stage.data() + of_at, object_of.data(), (size_t)n_src * 4);
-        for (uint32_t g = 0; g < n_objects; ++g)
-            stage[sel_at + g] = hbec::hash_select_bits(n, select + (size_t)select_of[g] * n);
-    }
-    std::lock_guard<std::mutex> lk(plan->mp_mu);
-    rc = stage_begin(plan, stage, stream);
-    if (rc) return rc;
-    const uint32_t* d_stage = plan->d_mstage;
-    g_hashfiles_launches.fetch_add(1, std::memory_order_relaxed);
-    g_hashfiles_chains.fetch_add(chains.size(), std::memory_order_relaxed);
-    g_hashfiles_segments.fetch_add(segments, std::memory_order_relaxed);
-    hipError_t e = hbec::launch_md5_files(plan->d_hrecs, d_stage + objects_at,
-                                          reinterpret_cast<const hbec::FChain*>(d_stage), chains.size(), k, n,
-                                          d_filter, filter_bits, d_expected, d_digests,
-                                          d_expected ? d_bad : nullptr, stream, plan->shards);
-    if (e == hipSuccess && d_where) {
-        g_hashfiles_launches.fetch_add(1, std::memory_order_relaxed);
-        e = hbec::launch_hash_files_where(plan->d_hrecs, (uint32_t)n_src, d_stage + of_at, d_stage + sel_at, d_filter,
-                                          filter_bits, d_bad, d_where, stream);
-    }
-    rc = stage_end(plan, stream);
-    if (e != hipSuccess) return hip_fail(e, "launch md5_files");
-    return rc;
-}
-
 // The calls with one pattern for all (hbec_encode_plan, hbec_reconstruct_plan,
 // hbec_verify_plan) on a shards plan: the call with a pattern per entry, every
-// entry given pattern 0.
+// entry given pattern 0, through that call's exported entry point (plan_calls.cpp).
 template <class F>
 int uniform_mixed(const hbec_plan* plan, F&& call) {
     const std::vector<uint32_t> of((size_t)plan->n_src, 0u);
@@ -1745,8 +845,7 @@ int hbec_encode_plan(hbec_codec* codec, const hbec_plan* plan, void* hip_stream)
             std::vector<uint8_t> mask((size_t)k + m, 0);
             std::fill(mask.begin(), mask.begin() + k, (uint8_t)1);
             return uniform_mixed(plan, [&](const uint32_t* of) {
-                return reconstruct_plan_mixed(codec, plan, mask.data(), 1, of, false,
-                                              static_cast<hipStream_t>(hip_stream));
+                return hbec_reconstruct_plan_mixed(codec, plan, mask.data(), 1, of, 0, hip_stream);
             });
         }
         std::vector<uint8_t> mat((size_t)(k + m) * k);
@@ -1774,8 +873,7 @@ int hbec_reconstruct_plan(hbec_codec* codec, const hbec_plan* plan, const uint8_
         if (n_present < k) return fail(HBEC_ERR_TOO_FEW_SHARDS, "too few shards given");
         if (plan->shards)
             return uniform_mixed(plan, [&](const uint32_t* of) {
-                return reconstruct_plan_mixed(codec, plan, present, 1, of, data_only != 0,
-                                              static_cast<hipStream_t>(hip_stream));
+                return hbec_reconstruct_plan_mixed(codec, plan, present, 1, of, data_only, hip_stream);
             });
         std::vector<int> surv(k), outs(n);
         std::vector<uint8_t> rows((size_t)n * k);
@@ -1785,23 +883,6 @@ int hbec_reconstruct_plan(hbec_codec* codec, const hbec_plan* plan, const uint8_
         outs.resize(n_out);
         rows.resize((size_t)n_out * k);
         return run_plan(plan, surv, outs, rows, static_cast<hipStream_t>(hip_stream));
-    });
-}
-
-int hbec_reconstruct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                                const uint32_t* pattern_of, int data_only, void* hip_stream) {
-    return hbec::guarded("hbec_reconstruct_plan_mixed", [&]() -> int {
-        return reconstruct_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, data_only != 0,
-                                      static_cast<hipStream_t>(hip_stream));
-    });
-}
-
-int hbec_mixed_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
-    return hbec::guarded("hbec_mixed_plan_stats", [&]() -> int {
-        if (!kernel_launches || !per_stripe_calls) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-        *kernel_launches = g_mplan_launches.load(std::memory_order_relaxed);
-        *per_stripe_calls = g_mplan_per_stripe.load(std::memory_order_relaxed);
-        return HBEC_OK;
     });
 }
 
@@ -1823,173 +904,6 @@ int hbec_set_stripes_grid_cap(int blocks) {
     });
 }
 
-int hbec_mixed_plan_tile_bytes(void) { return (int)hbec::mixed_plan_tile_bytes(); }
-
-int hbec_set_mixed_plan_chunk_tiles(uint64_t tiles) {
-    return hbec::guarded("hbec_set_mixed_plan_chunk_tiles", [&]() -> int {
-        g_mplan_chunk_override.store(tiles, std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
-int hbec_verify_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                           const uint32_t* pattern_of, uint32_t* d_flags, void* hip_stream) {
-    return hbec::guarded("hbec_verify_plan_mixed", [&]() -> int {
-        return verify_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, d_flags,
-                                 static_cast<hipStream_t>(hip_stream));
-    });
-}
-
-int hbec_verify_mixed_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
-    return hbec::guarded("hbec_verify_mixed_plan_stats", [&]() -> int {
-        if (!kernel_launches || !per_stripe_calls) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-        *kernel_launches = g_vmplan_launches.load(std::memory_order_relaxed);
-        *per_stripe_calls = g_vmplan_per_stripe.load(std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
-int hbec_verify_mixed_plan_tile_bytes(void) { return (int)hbec::verify_mixed_plan_tile_bytes(); }
-
-int hbec_set_verify_mixed_plan_chunk_tiles(uint64_t tiles) {
-    return hbec::guarded("hbec_set_verify_mixed_plan_chunk_tiles", [&]() -> int {
-        g_vmplan_chunk_override.store(tiles, std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
-int hbec_repair_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                           const uint32_t* pattern_of, int data_only, uint32_t* d_flags, void* hip_stream) {
-    return hbec::guarded("hbec_repair_plan_mixed", [&]() -> int {
-        return repair_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, data_only != 0, d_flags,
-                                 static_cast<hipStream_t>(hip_stream));
-    });
-}
-
-int hbec_repair_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
-    return hbec::guarded("hbec_repair_plan_stats", [&]() -> int {
-        if (!kernel_launches || !per_stripe_calls) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-        *kernel_launches = g_rplan_launches.load(std::memory_order_relaxed);
-        *per_stripe_calls = g_rplan_per_stripe.load(std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
-int hbec_repair_plan_tile_bytes(void) { return (int)hbec::repair_plan_tile_bytes(); }
-
-int hbec_set_repair_plan_chunk_tiles(uint64_t tiles) {
-    return hbec::guarded("hbec_set_repair_plan_chunk_tiles", [&]() -> int {
-        g_rplan_chunk_override.store(tiles, std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
-static_assert(HBEC_LOC_BAD == hbec::kLocBad && HBEC_LOC_SKIPPED == hbec::kLocSkipped &&
-                  HBEC_LOC_NOTHING == hbec::kLocNothing && HBEC_LOC_CLEAN == hbec::kLocClean &&
-                  HBEC_LOC_AMBIGUOUS == hbec::kLocAmbiguous && HBEC_LOC_MULTIPLE == hbec::kLocMultiple &&
-                  HBEC_LOC_UNCHECKED == hbec::kLocUnchecked,
-              "include/hbec.h and locate.h disagree");
-
-int hbec_locate_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                           const uint32_t* pattern_of, const uint32_t* d_flags, uint32_t* d_where, void* hip_stream) {
-    return hbec::guarded("hbec_locate_plan_mixed", [&]() -> int {
-        return locate_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, d_flags, d_where,
-                                 static_cast<hipStream_t>(hip_stream));
-    });
-}
-
-int hbec_locate_decode(int k, int m, const uint8_t* present, uint32_t where) {
-    if (!present || k < 1 || m < 0 || k + m > 256) return HBEC_ERR_INVALID_ARG;
-    return hbec::loc_decode(k, m, present, where);
-}
-
-int hbec_locate_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries) {
-    return hbec::guarded("hbec_locate_plan_stats", [&]() -> int {
-        if (!kernel_launches || !skipped_entries) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-        *kernel_launches = g_locplan_launches.load(std::memory_order_relaxed);
-        *skipped_entries = g_locplan_skipped.load(std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
-int hbec_locate_plan_tile_bytes(void) { return (int)hbec::locate_plan_tile_bytes(); }
-
-int hbec_set_locate_plan_chunk_tiles(uint64_t tiles) {
-    return hbec::guarded("hbec_set_locate_plan_chunk_tiles", [&]() -> int {
-        g_locplan_chunk_override.store(tiles, std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
-static_assert(HBEC_HEAL_DONE == hbec::kHealDone && HBEC_HEAL_UNNAMED == hbec::kHealUnnamed,
-              "include/hbec.h and heal.h disagree");
-
-int hbec_heal_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                         const uint32_t* pattern_of, const uint32_t* d_where, uint32_t* d_flags, void* hip_stream) {
-    return hbec::guarded("hbec_heal_plan_mixed", [&]() -> int {
-        return heal_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, d_where, d_flags,
-                               static_cast<hipStream_t>(hip_stream));
-    });
-}
-
-int hbec_heal_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries) {
-    return hbec::guarded("hbec_heal_plan_stats", [&]() -> int {
-        if (!kernel_launches || !skipped_entries) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-        *kernel_launches = g_healplan_launches.load(std::memory_order_relaxed);
-        *skipped_entries = g_healplan_skipped.load(std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
-int hbec_heal_plan_tile_bytes(void) { return (int)hbec::heal_plan_tile_bytes(); }
-
-int hbec_set_heal_plan_chunk_tiles(uint64_t tiles) {
-    return hbec::guarded("hbec_set_heal_plan_chunk_tiles", [&]() -> int {
-        g_healplan_chunk_override.store(tiles, std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
-int hbec_hash_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* select, uint32_t n_select,
-                         const uint32_t* select_of, const uint32_t* d_filter, uint32_t filter_bits,
-                         const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad, uint32_t* d_where,
-                         void* hip_stream) {
-    return hbec::guarded("hbec_hash_plan_mixed", [&]() -> int {
-        return hash_plan_mixed(codec, plan, select, n_select, select_of, d_filter, filter_bits, d_expected, d_digests,
-                               d_bad, d_where, static_cast<hipStream_t>(hip_stream));
-    });
-}
-
-int hbec_hash_plan_stats(uint64_t* kernel_launches, uint64_t* chains) {
-    return hbec::guarded("hbec_hash_plan_stats", [&]() -> int {
-        if (!kernel_launches || !chains) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-        *kernel_launches = g_hashplan_launches.load(std::memory_order_relaxed);
-        *chains = g_hashplan_chains.load(std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
-int hbec_hash_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
-                         const uint8_t* select, uint32_t n_select, const uint32_t* select_of,
-                         const uint32_t* d_filter, uint32_t filter_bits, const uint8_t* d_expected,
-                         uint8_t* d_digests, uint32_t* d_bad, uint32_t* d_where, void* hip_stream) {
-    return hbec::guarded("hbec_hash_plan_files", [&]() -> int {
-        return hash_plan_files(codec, plan, object_start, n_objects, select, n_select, select_of, d_filter,
-                               filter_bits, d_expected, d_digests, d_bad, d_where,
-                               static_cast<hipStream_t>(hip_stream));
-    });
-}
-
-int hbec_hash_files_stats(uint64_t* kernel_launches, uint64_t* chains, uint64_t* segments) {
-    return hbec::guarded("hbec_hash_files_stats", [&]() -> int {
-        if (!kernel_launches || !chains || !segments) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-        *kernel_launches = g_hashfiles_launches.load(std::memory_order_relaxed);
-        *chains = g_hashfiles_chains.load(std::memory_order_relaxed);
-        *segments = g_hashfiles_segments.load(std::memory_order_relaxed);
-        return HBEC_OK;
-    });
-}
-
 int hbec_verify_plan(hbec_codec* codec, const hbec_plan* plan, uint32_t* d_flags, void* hip_stream) {
     return hbec::guarded("hbec_verify_plan", [&]() -> int {
         if (!codec || !plan || (!d_flags && plan->n_src)) return fail(HBEC_ERR_INVALID_ARG, "null argument");
@@ -2001,7 +915,7 @@ int hbec_verify_plan(hbec_codec* codec, const hbec_plan* plan, uint32_t* d_flags
             // every shard present: the m parity shards are the checked ones, bit 0 only
             const std::vector<uint8_t> mask((size_t)k + m, 1);
             return uniform_mixed(plan, [&](const uint32_t* of) {
-                return verify_plan_mixed(codec, plan, mask.data(), 1, of, d_flags, stream);
+                return hbec_verify_plan_mixed(codec, plan, mask.data(), 1, of, d_flags, hip_stream);
             });
         }
         if (plan->n_tiles > 0 && hbec::vp_tiles_shape(k, m)) {

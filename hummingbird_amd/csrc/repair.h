@@ -54,8 +54,6 @@ inline uint32_t rp_pattern(std::vector<uint32_t>& buf, int k, const int* survivo
     return mp_pattern(buf, k, survivors, idx, r_out + r_chk, rows.data());
 }
 
-uint32_t repair_plan_tile_bytes();
-
 // Tiles [0, n_tiles) of `tiles`: every tile whose entry's word has 1..r rows in
 // total (r >= 1: the largest total in the call) rebuilds its r_o outputs and
 // ORs 1 into flags[entry] when one of its r_c checked shards differs from what

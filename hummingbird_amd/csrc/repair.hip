@@ -29,6 +29,7 @@
 
 #include "gf_device.h"
 #include "kernels.h"
+#include "planwalk.h"
 #include "repair.h"
 #include "repair_tile.h"
 #include "unaligned_tile.h"
@@ -156,26 +157,13 @@ static const void* repair_mixed_plan_kernel(int r, bool rows) {
     return nullptr;
 }
 
-uint32_t repair_plan_tile_bytes() { return (uint32_t)kUnalignedU * kUnalignedWindow; }
-
 hipError_t launch_repair_mixed_plan(int k, int r, const MRec* recs, const MTile* tiles, uint32_t n_tiles,
                                     const uint32_t* pat_of, const uint32_t* pats, uint32_t* flags, int cus,
                                     hipStream_t stream, bool rows) {
-    const void* fn = repair_mixed_plan_kernel(r, rows);
-    if (!fn || k < 1 || k > kOddMaxK || cus < 1) return hipErrorInvalidValue;
-    if (n_tiles == 0) return hipSuccess;
     static std::atomic<int> occ[2][kMaxR + 1] = {};  // blocks per CU, asked once per instance
-    int per_cu = occ[rows][r].load(std::memory_order_relaxed);
-    if (per_cu == 0) {
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlockThreads, 0);
-        if (e != hipSuccess) return e;
-        occ[rows][r].store(std::max(1, per_cu), std::memory_order_relaxed);
-    }
-    constexpr uint64_t wpb = kBlockThreads / 64;
-    const uint64_t grid =
-        std::max<uint64_t>(1, std::min<uint64_t>((n_tiles + wpb - 1) / wpb, (uint64_t)cus * std::max(1, per_cu)));
+    const void* fn = repair_mixed_plan_kernel(r, rows);
     void* args[] = {&recs, &tiles, &n_tiles, &pat_of, &pats, &k, &flags};
-    return hipLaunchKernel(fn, dim3((uint32_t)grid), dim3(kBlockThreads), args, 0, stream);
+    return launch_plan_walk(fn, fn ? &occ[rows][r] : nullptr, k, n_tiles, cus, args, stream);
 }
 
 }  // namespace hbec

@@ -55,8 +55,6 @@ inline uint32_t vm_pattern(std::vector<uint32_t>& buf, int k, const int* survivo
     return mp_pattern(buf, k, survivors, checked, r, rows);
 }
 
-uint32_t verify_mixed_plan_tile_bytes();
-
 // Tiles [0, n_tiles) of `tiles`: every tile whose entry's word has 1..r checked
 // shards (r >= 1: the largest count in the call) is compared and ORs 1 into
 // flags[entry] on a mismatch; tile 0 of an entry whose word is kVmNothing ORs 2.

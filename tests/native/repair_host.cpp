@@ -81,7 +81,7 @@ static int records() {
 
 static int routing() {
     using namespace hbec;
-    const uint64_t T = 3968;  // repair_plan_tile_bytes(): kUnalignedU windows of kUnalignedWindow
+    const uint64_t T = 3968;  // mixed_plan_tile_bytes(): kUnalignedU windows of kUnalignedWindow
     CHECK(rp_route(4, 2, 0) == kVmSkip && rp_route(13, 4, 0) == kVmSkip);
     for (uint64_t s : {(uint64_t)1, T - 1, T, T + 1, kPos32MaxShard}) {
         CHECK(rp_route(4, 2, s) == kVmKernel && rp_route(12, 4, s) == kVmKernel && rp_route(1, 1, s) == kVmKernel);

@@ -93,7 +93,7 @@ static int words() {
 
 static int routing() {
     using namespace hbec;
-    const uint64_t T = 3968;  // verify_mixed_plan_tile_bytes(): kUnalignedU windows of kUnalignedWindow
+    const uint64_t T = 3968;  // mixed_plan_tile_bytes(): kUnalignedU windows of kUnalignedWindow
     CHECK(vm_route(4, 2, 0) == kVmSkip && vm_route(13, 4, 0) == kVmSkip);
     for (uint64_t s : {(uint64_t)1, T - 1, T, T + 1, kPos32MaxShard}) {
         CHECK(vm_route(4, 2, s) == kVmKernel && vm_route(12, 4, s) == kVmKernel && vm_route(1, 1, s) == kVmKernel);

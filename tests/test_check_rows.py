@@ -128,28 +128,9 @@ def test_verify_plan_mixed_arguments_on_a_plan_of_zero_length_entries():
 def test_verify_mixed_plan_instances_use_no_scratch_and_no_lds():
     """RMAX = 1..4 (K is a run-time argument): bases, indices and tables come
     through scalar loads, nothing is indexed in private memory."""
-    import shutil
-    import subprocess
-    import tempfile
-    from pathlib import Path
-
-    import yaml
-
     import test_kernel_resources as KR
 
-    assert KR.LIB.exists(), "libhbec.so not built"
-    readelf = str(KR.READELF) if KR.READELF.exists() else shutil.which("llvm-readelf")
-    assert readelf, "llvm-readelf not found"
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for n, co in enumerate(KR._code_objects(KR.LIB.read_bytes())):
-            if b"gf_verify_mixed_plan" not in co:
-                continue
-            f = Path(td) / f"co{n}.o"
-            f.write_bytes(co)
-            text = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True, check=True).stdout
-            meta = yaml.safe_load(text.split("---", 1)[1].split("\n...", 1)[0])
-            found.update({k[".name"]: k for k in meta["amdhsa.kernels"] if "gf_verify_mixed_planILi" in k[".name"]})
+    found = KR.kernels("gf_verify_mixed_planILi")
     assert len(found) == 4, sorted(found)
     for r in range(1, 5):
         assert any(f"gf_verify_mixed_planILi{r}E" in nm for nm in found), r

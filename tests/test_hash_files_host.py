@@ -10,9 +10,7 @@ The program is compiled with the host compiler and run directly; it links no
 libhbec and touches no device."""
 import ctypes as C
 import re
-import shutil
 import subprocess
-import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -144,31 +142,10 @@ def test_python_wrapper_checks_its_arrays():
         plan.hash_files([0, -1, 3])
 
 
-def _files_kernels():
-    """{kernel name: metadata} of md5_files and hash_files_where in the library."""
-    import yaml
-
+def test_md5_files_uses_no_scratch_and_no_lds():
     import test_kernel_resources as KR
 
-    assert KR.LIB.exists(), "libhbec.so not built"
-    readelf = str(KR.READELF) if KR.READELF.exists() else shutil.which("llvm-readelf")
-    assert readelf, "llvm-readelf not found"
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for n, co in enumerate(KR._code_objects(KR.LIB.read_bytes())):
-            if b"md5_files" not in co:
-                continue
-            f = Path(td) / f"co{n}.o"
-            f.write_bytes(co)
-            text = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True, check=True).stdout
-            meta = yaml.safe_load(text.split("---", 1)[1].split("\n...", 1)[0])
-            found.update({k[".name"]: k for k in meta["amdhsa.kernels"]
-                          if "9md5_filesE" in k[".name"] or "16hash_files_whereE" in k[".name"]})
-    return found
-
-
-def test_md5_files_uses_no_scratch_and_no_lds():
-    ks = _files_kernels()
+    ks = {**KR.kernels("9md5_filesE"), **KR.kernels("16hash_files_whereE")}
     files = [k for nm, k in ks.items() if "9md5_filesE" in nm]
     where = [k for nm, k in ks.items() if "16hash_files_whereE" in nm]
     assert len(files) == 1 and len(where) == 1, sorted(ks)

@@ -8,9 +8,7 @@ from the library's code-object metadata.
 The program is compiled with the host compiler and run directly; it links no
 libhbec and touches no device."""
 import ctypes as C
-import shutil
 import subprocess
-import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -122,31 +120,10 @@ def test_python_wrapper_checks_its_arrays():
         plan.hash_mixed(np.ones((3, K + M + 1)))
 
 
-def _md5_plan_kernels():
-    """{kernel name: metadata} of every md5_plan / hash_where in the library."""
-    import yaml
-
+def test_md5_plan_uses_no_scratch_and_no_lds():
     import test_kernel_resources as KR
 
-    assert KR.LIB.exists(), "libhbec.so not built"
-    readelf = str(KR.READELF) if KR.READELF.exists() else shutil.which("llvm-readelf")
-    assert readelf, "llvm-readelf not found"
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for n, co in enumerate(KR._code_objects(KR.LIB.read_bytes())):
-            if b"md5_plan" not in co:
-                continue
-            f = Path(td) / f"co{n}.o"
-            f.write_bytes(co)
-            text = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True, check=True).stdout
-            meta = yaml.safe_load(text.split("---", 1)[1].split("\n...", 1)[0])
-            found.update({k[".name"]: k for k in meta["amdhsa.kernels"]
-                          if "8md5_planE" in k[".name"] or "10hash_whereE" in k[".name"]})
-    return found
-
-
-def test_md5_plan_uses_no_scratch_and_no_lds():
-    ks = _md5_plan_kernels()
+    ks = {**KR.kernels("8md5_planE"), **KR.kernels("10hash_whereE")}
     plan = [k for nm, k in ks.items() if "8md5_planE" in nm]
     where = [k for nm, k in ks.items() if "10hash_whereE" in nm]
     assert len(plan) >= 1 and len(where) == 1, sorted(ks)

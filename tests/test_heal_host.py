@@ -12,7 +12,6 @@ written to a file the program reads, so every staged record of a mask with one
 shard left out is checked against the library's own rows of that mask."""
 import ctypes as C
 import itertools
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -116,30 +115,6 @@ def test_new_symbols_are_exported_and_declared():
     assert hasattr(B.StripePlan, "heal_mixed")
 
 
-def _kernels(name):
-    """{kernel name: metadata} of every instance of `name` in the library."""
-    import tempfile
-
-    import yaml
-
-    import test_kernel_resources as KR
-
-    assert KR.LIB.exists(), "libhbec.so not built"
-    readelf = str(KR.READELF) if KR.READELF.exists() else shutil.which("llvm-readelf")
-    assert readelf, "llvm-readelf not found"
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for n, co in enumerate(KR._code_objects(KR.LIB.read_bytes())):
-            if name.encode() not in co:
-                continue
-            f = Path(td) / f"co{n}.o"
-            f.write_bytes(co)
-            text = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True, check=True).stdout
-            meta = yaml.safe_load(text.split("---", 1)[1].split("\n...", 1)[0])
-            found.update({k[".name"]: k for k in meta["amdhsa.kernels"] if f"{name}ILi" in k[".name"]})
-    return found
-
-
 def waves_per_simd(vgprs):
     """gfx950: 512 VGPRs per SIMD lane, allocated in blocks of 8, at most 8 waves."""
     return min(8, 512 // (-(-vgprs // 8) * 8))
@@ -149,7 +124,9 @@ def test_heal_plan_instances_use_no_scratch_and_no_lds_and_keep_repairs_occupanc
     """RMAX = 1..4: no private memory, no LDS, no spilled VGPR, and as many
     waves per SIMD as the gf_repair_mixed_plan instance of the same RMAX
     (5 / 4 / 3 / 3)."""
-    heal, repair = _kernels("gf_heal_mixed_plan"), _kernels("gf_repair_mixed_plan")
+    import test_kernel_resources as KR
+
+    heal, repair = KR.kernels("gf_heal_mixed_planILi"), KR.kernels("gf_repair_mixed_planILi")
     assert len(heal) == 4 and len(repair) == 4, (sorted(heal), sorted(repair))
     for r in range(1, 5):
         (h,) = [k for nm, k in heal.items() if f"gf_heal_mixed_planILi{r}E" in nm]

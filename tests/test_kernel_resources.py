@@ -15,6 +15,7 @@ llvm-readelf and pins the resource facts the round-3 tuning depends on
 """
 from __future__ import annotations
 
+import functools
 import shutil
 import struct
 import subprocess
@@ -48,13 +49,16 @@ def _code_objects(blob: bytes):
         i += len(MAGIC)
 
 
-@pytest.fixture(scope="module")
-def kernels():
-    if not LIB.exists():
-        pytest.skip("libhbec.so not built")
-    readelf = str(READELF) if READELF.exists() else shutil.which("llvm-readelf")
-    if not readelf:
-        pytest.skip("llvm-readelf not found")
+def _readelf():
+    return str(READELF) if READELF.exists() else shutil.which("llvm-readelf")
+
+
+@functools.lru_cache(maxsize=None)
+def _library_kernels():
+    """{kernel name: metadata} of every gfx950 kernel in the library, read once a session."""
+    assert LIB.exists(), "libhbec.so not built"
+    readelf = _readelf()
+    assert readelf, "llvm-readelf not found"
     out = {}
     with tempfile.TemporaryDirectory() as td:
         for n, co in enumerate(_code_objects(LIB.read_bytes())):
@@ -68,6 +72,22 @@ def kernels():
                 out[k[".name"]] = k
     assert out, "no gfx950 code objects found in libhbec.so"
     return out
+
+
+def kernels(name):
+    """{kernel name: metadata} of the library's kernels whose mangled name contains `name`
+    ("gf_mixed_planILi": the instances of that template and of no other).  The tests of the
+    other files that pin a kernel's resources read them here."""
+    return {nm: k for nm, k in _library_kernels().items() if name in nm}
+
+
+@pytest.fixture(scope="module", name="kernels")
+def all_kernels():
+    if not LIB.exists():
+        pytest.skip("libhbec.so not built")
+    if not _readelf():
+        pytest.skip("llvm-readelf not found")
+    return kernels("")
 
 
 def _one(kernels, mangled):

@@ -68,25 +68,9 @@ def test_locate_plan_instances_use_no_scratch_and_no_lds():
     counter, so nothing is indexed in private memory, and it must not cost the
     hot path a wave: each instance stays in the occupancy step of its Verify
     twin (96 / 116 / 134 / 152 VGPRs: 5 / 4 / 3 / 3 waves per SIMD)."""
-    import tempfile
-
-    import yaml
-
     import test_kernel_resources as KR
 
-    assert KR.LIB.exists(), "libhbec.so not built"
-    readelf = str(KR.READELF) if KR.READELF.exists() else shutil.which("llvm-readelf")
-    assert readelf, "llvm-readelf not found"
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for n, co in enumerate(KR._code_objects(KR.LIB.read_bytes())):
-            if b"gf_locate_mixed_plan" not in co:
-                continue
-            f = Path(td) / f"co{n}.o"
-            f.write_bytes(co)
-            text = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True, check=True).stdout
-            meta = yaml.safe_load(text.split("---", 1)[1].split("\n...", 1)[0])
-            found.update({k[".name"]: k for k in meta["amdhsa.kernels"] if "gf_locate_mixed_planILi" in k[".name"]})
+    found = KR.kernels("gf_locate_mixed_planILi")
     assert len(found) == 4, sorted(found)
     step = {1: 96, 2: 128, 3: 168, 4: 168}  # the largest allocation with Verify's waves per SIMD
     for r in range(1, 5):

@@ -3,22 +3,14 @@ before anything is queued (as hbec_reconstruct_batch's do), a batch with
 nothing to rebuild is a no-op, and every shipped gf_apply_mixed instance
 (K = 1..8 x R = 1..4) runs without scratch memory."""
 import ctypes as C
-import shutil
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 import pytest
-import yaml
 
+import test_kernel_resources as KR
 from hummingbird_amd import _native as N
-from hummingbird_amd import isa_check
 from hummingbird_amd import reedsolomon as RS
 
-ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "hummingbird_amd" / "libhbec.so"
-READELF = Path("/opt/rocm/lib/llvm/bin/llvm-readelf")
 K, M = 4, 2
 U32P = C.POINTER(C.c_uint32)
 
@@ -135,21 +127,7 @@ def test_chunk_hook_and_stats_answer():
 def test_mixed_instances_use_no_scratch():
     """K = 1..8 x R = 1..4: the tables of the largest instances (8+3: 120
     words, 8+4: 160) stay in registers."""
-    assert LIB.exists(), "libhbec.so not built"
-    readelf = str(READELF) if READELF.exists() else shutil.which("llvm-readelf")
-    assert readelf, "llvm-readelf not found"
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for n, co in enumerate(isa_check.code_objects(LIB.read_bytes())):
-            if b"gf_apply_mixed" not in co:
-                continue
-            f = Path(td) / f"co{n}.o"
-            f.write_bytes(co)
-            text = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True, check=True).stdout
-            meta = yaml.safe_load(text.split("---", 1)[1].split("\n...", 1)[0])
-            for k in meta["amdhsa.kernels"]:
-                if "gf_apply_mixedILi" in k[".name"]:
-                    found[k[".name"]] = k
+    found = KR.kernels("gf_apply_mixedILi")
     assert len(found) >= 32, sorted(found)
     for kk in range(1, 9):
         for r in range(1, 5):

@@ -5,23 +5,15 @@ rebuild is a no-op; and every shipped gf_mixed_plan instance (R = 1..4) runs
 without scratch memory.  The plans here are built from zero-length entries
 only, which need no device memory."""
 import ctypes as C
-import shutil
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 import pytest
-import yaml
 
+import test_kernel_resources as KR
 from hummingbird_amd import _native as N
 from hummingbird_amd import batch as B
-from hummingbird_amd import isa_check
 from hummingbird_amd import reedsolomon as RS
 
-ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "hummingbird_amd" / "libhbec.so"
-READELF = Path("/opt/rocm/lib/llvm/bin/llvm-readelf")
 K, M = 4, 2
 U32P = C.POINTER(C.c_uint32)
 FULL = [1] * (K + M)
@@ -135,21 +127,7 @@ def test_chunk_hook_stats_and_tile_bytes_answer():
 def test_mixed_plan_instances_use_no_scratch():
     """R = 1..4 (K is a run-time argument): bases, indices and tables come
     through scalar loads, nothing is indexed in private memory."""
-    assert LIB.exists(), "libhbec.so not built"
-    readelf = str(READELF) if READELF.exists() else shutil.which("llvm-readelf")
-    assert readelf, "llvm-readelf not found"
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for n, co in enumerate(isa_check.code_objects(LIB.read_bytes())):
-            if b"gf_mixed_plan" not in co:
-                continue
-            f = Path(td) / f"co{n}.o"
-            f.write_bytes(co)
-            text = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True, check=True).stdout
-            meta = yaml.safe_load(text.split("---", 1)[1].split("\n...", 1)[0])
-            for k in meta["amdhsa.kernels"]:
-                if "gf_mixed_planILi" in k[".name"]:
-                    found[k[".name"]] = k
+    found = KR.kernels("gf_mixed_planILi")
     assert len(found) == 4, sorted(found)
     for r in range(1, 5):
         assert any(f"gf_mixed_planILi{r}E" in nm for nm in found), r

@@ -12,12 +12,10 @@ import ctypes as C
 import json
 import re
 import subprocess
-import tempfile
 from pathlib import Path
 
 import numpy as np
 import pytest
-import yaml
 
 import test_kernel_resources as KR
 import test_repair_mixed_host as RH
@@ -281,19 +279,7 @@ FAMILIES = ("gf_mixed_plan", "gf_verify_mixed_plan", "gf_repair_mixed_plan", "gf
 
 @pytest.fixture(scope="module")
 def kernels():
-    assert KR.LIB.exists(), "libhbec.so not built"
-    assert KR.READELF.exists(), "llvm-readelf not found"
-    out = {}
-    with tempfile.TemporaryDirectory() as td:
-        for n, co in enumerate(KR._code_objects(KR.LIB.read_bytes())):
-            f = Path(td) / f"co{n}.o"
-            f.write_bytes(co)
-            text = subprocess.run([str(KR.READELF), "--notes", str(f)], capture_output=True, text=True,
-                                  check=True).stdout
-            meta = yaml.safe_load(text.split("---", 1)[1].split("\n...", 1)[0])
-            for k in meta["amdhsa.kernels"]:
-                out[k[".name"]] = k
-    return out
+    return KR.kernels("")
 
 
 def _figures(k):

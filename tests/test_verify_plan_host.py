@@ -3,23 +3,14 @@ answers before anything is queued and without touching a device (a plan of
 zero-length stripes is built on the host alone), m = 0 and all-empty inputs are
 no-ops, and every shipped plan Verify kernel runs without scratch memory."""
 import ctypes as C
-import shutil
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 import pytest
-import yaml
 
+import test_kernel_resources as KR
 from hummingbird_amd import _native as N
 from hummingbird_amd import batch as B
-from hummingbird_amd import isa_check
 from hummingbird_amd import reedsolomon as RS
-
-ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "hummingbird_amd" / "libhbec.so"
-READELF = Path("/opt/rocm/lib/llvm/bin/llvm-readelf")
 
 
 def _empty_plan(enc, n=3, objects=False):
@@ -128,21 +119,7 @@ def test_stats_and_tile_bytes_answer():
 def test_plan_verify_kernels_use_no_scratch():
     """gf_verify_tiles K = 1..8 x R = 1..4 and gf_verify_recs / its tail R =
     1..4: no private segment; only gf_verify_recs uses LDS (its tables, < 1 KiB)."""
-    assert LIB.exists(), "libhbec.so not built"
-    readelf = str(READELF) if READELF.exists() else shutil.which("llvm-readelf")
-    assert readelf, "llvm-readelf not found"
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for n, co in enumerate(isa_check.code_objects(LIB.read_bytes())):
-            if b"gf_verify_recs" not in co:
-                continue
-            f = Path(td) / f"co{n}.o"
-            f.write_bytes(co)
-            text = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True, check=True).stdout
-            meta = yaml.safe_load(text.split("---", 1)[1].split("\n...", 1)[0])
-            for k in meta["amdhsa.kernels"]:
-                if "gf_verify_tiles" in k[".name"] or "gf_verify_recs" in k[".name"]:
-                    found[k[".name"]] = k
+    found = {**KR.kernels("gf_verify_tiles"), **KR.kernels("gf_verify_recs")}
     for kk in range(1, 9):
         for r in range(1, 5):
             assert any(f"gf_verify_tilesILi{kk}ELi{r}E" in nm for nm in found), (kk, r)
