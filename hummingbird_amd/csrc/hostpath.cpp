@@ -19,14 +19,17 @@
 // ring entirely.  The stripe kernel reads their data shards and writes their
 // parity in place over PCIe, so there is no CPU copy and no DMA call per
 // chunk; only 32-B tile records travel.
+//
+// What is cut where (routes, pieces, chunks, the records of a slot) is decided
+// by the HIP-free rules of hostcut.h.  This file owns the ring and queues the
+// work: host_run_on picks the route, zero_copy_run (over walk_slots) codes pinned
+// stripes, ring_run the staged ones, verify_host_run_on serves hbec_verify_host.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
-#include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -36,6 +39,7 @@
 
 #include "../../include/hbec.h"
 #include "gf256.h"
+#include "hostcut.h"
 #include "internal.h"
 #include "kernels.h"
 #include "pool.h"
@@ -45,15 +49,6 @@ using hbec::fail;
 using hbec::hip_fail;
 
 namespace {
-
-// One column piece of one stripe: columns [col, col+len) of its K inputs / R outputs.
-struct Piece {
-    uint64_t stripe;
-    uint64_t col;
-    uint64_t len;   // bytes (<= shard_len - col)
-    uint64_t lpad;  // len rounded up to 16
-    uint64_t in_off, out_off;  // offsets of this piece in the slot's IN / OUT regions
-};
 
 constexpr int kSlots = 3;
 
@@ -67,55 +62,44 @@ struct Ring {
     int cus = 0;  // compute units of dev (grid sizing), read once
     size_t in_cap = 0, out_cap = 0, tile_cap = 0;
     hipStream_t s_h2d = nullptr, s_cmp = nullptr, s_d2h = nullptr;
-    uint8_t* pin_in[kSlots] = {};
-    uint8_t* pin_out[kSlots] = {};
-    uint8_t* dev_in[kSlots] = {};
-    uint8_t* dev_out[kSlots] = {};
-    hbec::TileRec* pin_tiles[kSlots] = {};
-    hbec::TileRec* dev_tiles[kSlots] = {};
+    uint8_t *pin_in[kSlots] = {}, *pin_out[kSlots] = {}, *dev_in[kSlots] = {}, *dev_out[kSlots] = {};
+    hbec::TileRec *pin_tiles[kSlots] = {}, *dev_tiles[kSlots] = {};
     hipEvent_t ev_h2d[kSlots] = {}, ev_cmp[kSlots] = {}, ev_done[kSlots] = {};
-    // ShardHash (hbec_encode_host_md5), created on first use: n_arenas device
-    // hash arenas (HBEC_HASH_ARENAS, default 2, of HBEC_HASH_ARENA_MB, default
-    // 1024; 2 x 3 GiB: pinned 4+2 encode+hash 1.14 x encode alone instead of
-    // 1.21 x, profiles/r02_host_md5_arenas.jsonl).  A chunk's shards land in the current arena (copied D2D after the
-    // ring's kernel, or written by the mirrored zero-copy kernel); a full
-    // arena is hashed by ONE md5_list launch on its own stream while the next
-    // arenas fill, so hashing hides behind the PCIe stream, and the hashes of
-    // several arenas may run at once.
+    // ShardHash (hbec_encode_host_md5), created on first use: n_arenas device hash arenas
+    // (HBEC_HASH_ARENAS, default 2, of HBEC_HASH_ARENA_MB, default 1024; 2 x 3 GiB: pinned 4+2
+    // encode+hash 1.14 x encode alone instead of 1.21 x, profiles/r02_host_md5_arenas.jsonl).  A
+    // chunk's shards land in the current arena (copied D2D after the ring's kernel, or written by
+    // the mirrored zero-copy kernel); a full arena is hashed by ONE md5_list launch on its own
+    // stream while the next arenas fill, so hashing hides behind the PCIe stream, and the hashes
+    // of several arenas may run at once.
     static constexpr int kArenas = 8;
     int n_arenas = 0;
     hipStream_t s_md5[kArenas] = {};
     uint8_t* arena[kArenas] = {};
     size_t arena_cap = 0, arena_rec_cap = 0;
-    uint64_t* pin_md5rec[kArenas] = {};
-    uint64_t* dev_md5rec[kArenas] = {};
+    uint64_t *pin_md5rec[kArenas] = {}, *dev_md5rec[kArenas] = {};
     hipEvent_t ev_arena_copied[kArenas] = {}, ev_arena_hashed[kArenas] = {};
     std::unique_ptr<hbec::Pool> pool;
 
     ~Ring() {
-        for (int i = 0; i < kSlots; ++i) {
-            if (pin_in[i]) (void)hipHostFree(pin_in[i]);
-            if (pin_out[i]) (void)hipHostFree(pin_out[i]);
-            if (pin_tiles[i]) (void)hipHostFree(pin_tiles[i]);
-            if (dev_in[i]) (void)hipFree(dev_in[i]);
-            if (dev_out[i]) (void)hipFree(dev_out[i]);
-            if (dev_tiles[i]) (void)hipFree(dev_tiles[i]);
-            if (ev_h2d[i]) (void)hipEventDestroy(ev_h2d[i]);
-            if (ev_cmp[i]) (void)hipEventDestroy(ev_cmp[i]);
-            if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
-        }
-        for (int a = 0; a < kArenas; ++a) {
-            if (arena[a]) (void)hipFree(arena[a]);
-            if (pin_md5rec[a]) (void)hipHostFree(pin_md5rec[a]);
-            if (dev_md5rec[a]) (void)hipFree(dev_md5rec[a]);
-            if (ev_arena_copied[a]) (void)hipEventDestroy(ev_arena_copied[a]);
-            if (ev_arena_hashed[a]) (void)hipEventDestroy(ev_arena_hashed[a]);
-        }
+        auto drop = [](std::initializer_list<void*> pinned, std::initializer_list<void*> device,
+                       std::initializer_list<hipEvent_t> events) {
+            for (void* p : pinned)
+                if (p) (void)hipHostFree(p);
+            for (void* p : device)
+                if (p) (void)hipFree(p);
+            for (hipEvent_t e : events)
+                if (e) (void)hipEventDestroy(e);
+        };
+        for (int i = 0; i < kSlots; ++i)
+            drop({pin_in[i], pin_out[i], pin_tiles[i]}, {dev_in[i], dev_out[i], dev_tiles[i]},
+                 {ev_h2d[i], ev_cmp[i], ev_done[i]});
         for (int a = 0; a < kArenas; ++a)
-            if (s_md5[a]) (void)hipStreamDestroy(s_md5[a]);
-        if (s_h2d) (void)hipStreamDestroy(s_h2d);
-        if (s_cmp) (void)hipStreamDestroy(s_cmp);
-        if (s_d2h) (void)hipStreamDestroy(s_d2h);
+            drop({pin_md5rec[a]}, {arena[a], dev_md5rec[a]}, {ev_arena_copied[a], ev_arena_hashed[a]});
+        for (hipStream_t s : s_md5)
+            if (s) (void)hipStreamDestroy(s);
+        for (hipStream_t s : {s_h2d, s_cmp, s_d2h})
+            if (s) (void)hipStreamDestroy(s);
     }
 };
 
@@ -429,238 +413,102 @@ uint64_t hbec::pinned_device_addr(const void* p, uint64_t len) {
 namespace {
 using hbec::pinned_device_addr;
 
-struct ZcStripe {
-    uint64_t dev;  // device address of the stripe base
-    uint64_t shard_len;
-};
+namespace cut = hbec::cut;
+using cut::Pass;
+using cut::ZcStripe;
 
-// Code pinned stripes in place: tile records (rings of kSlots pinned/device
-// buffers) are the only host->device traffic; the kernel streams the shards
-// over PCIe.  One stream, so records, kernels and their reuse are ordered.
-int zero_copy_run(Ring* ring, const std::vector<ZcStripe>& zs, const std::vector<int>& in_idx,
-                  const std::vector<int>& out_idx, const std::vector<uint8_t>& rows) {
-    const int K = (int)in_idx.size();
-    const uint64_t tile = (uint64_t)hbec::stripes_tile_bytes(std::min(K, hbec::kStripeMaxK));
+// The slot rotation of every runner that hands a slot back when the kernel that read it is
+// done (ev_cmp): wait for the slot, let body(slot, more) queue its work, kernels on s_cmp, and
+// mark their end.  more: another slot follows.  There is always a first slot, so callers come
+// with at least one stripe or chunk.
+template <class Body>
+int walk_slots(Ring* ring, const char* wait_what, const char* event_what, Body body) {
+    bool more = true;
+    for (int c = 0; more; ++c) {
+        const int slot = c % kSlots;
+        hipError_t e = hipEventSynchronize(ring->ev_cmp[slot]);  // the slot's previous kernels are done
+        if (e != hipSuccess) return hip_fail(e, wait_what);
+        const int rc = body(slot, more);
+        if (rc) return rc;
+        e = hipEventRecord(ring->ev_cmp[slot], ring->s_cmp);
+        if (e != hipSuccess) return hip_fail(e, event_what);
+    }
+    return HBEC_OK;
+}
+
+// Records plus the slot's IN bytes to the device on the copy stream, and the
+// compute stream behind them (the ring and the staged Verify).
+int staged_upload(Ring* ring, int slot, size_t rec_bytes, uint64_t in_bytes, const char* what) {
+    hipError_t e = hipSuccess;
+    if (rec_bytes)
+        e = hipMemcpyAsync(ring->dev_tiles[slot], ring->pin_tiles[slot], rec_bytes, hipMemcpyHostToDevice, ring->s_h2d);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(ring->dev_in[slot], ring->pin_in[slot], in_bytes, hipMemcpyHostToDevice, ring->s_h2d);
+    if (e == hipSuccess) e = hipEventRecord(ring->ev_h2d[slot], ring->s_h2d);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ring->s_cmp, ring->ev_h2d[slot], 0);
+    return e != hipSuccess ? hip_fail(e, what) : HBEC_OK;
+}
+
+// Code pinned stripes in place: records (rings of kSlots pinned/device
+// buffers; TileRec and URec are both 32 B, so the slot buffers are shared) are
+// the only host->device traffic; the kernel streams the shards over PCIe.  One
+// stream, so records, kernels and their reuse are ordered.  recs is the record
+// kind (hostcut.h), launch its kernel.  With ps.d_digest (every stripe pinned)
+// the kernel also writes every shard column it holds (inputs and outputs) to a
+// device hash arena, so nothing crosses PCIe twice and no CPU copy runs; a full
+// arena is hashed by one md5_list launch while the kernel fills the next ones.
+template <class Recs, class Launch>
+int zero_copy_run(Ring* ring, const Recs& recs, const std::vector<ZcStripe>& zs, const Pass& ps, Launch launch) {
+    using Rec = typename Recs::Rec;
+    static_assert(sizeof(Rec) == sizeof(hbec::TileRec), "record slots are shared");
+    int rc = ps.d_digest ? ring_md5_init(*ring) : HBEC_OK;
+    if (rc) return rc;
+    ArenaCursor ac{ring, ring->s_cmp, ps.d_digest};
     size_t si = 0;
     uint64_t off = 0;
-    hipError_t e = hipSuccess;
-    for (int c = 0; si < zs.size(); ++c) {
-        const int slot = c % kSlots;
-        e = hipEventSynchronize(ring->ev_cmp[slot]);  // the slot's previous records are consumed
-        if (e != hipSuccess) return hip_fail(e, "zero-copy slot wait");
-        hbec::TileRec* rec = ring->pin_tiles[slot];
-        uint64_t nt = 0;
-        while (si < zs.size() && nt < ring->tile_cap) {
-            const ZcStripe& z = zs[si];
-            hbec::TileRec& t = rec[nt++];
-            t.in_addr = t.out_addr = z.dev + off;
-            t.in_stride = t.out_stride = (uint32_t)z.shard_len;
-            t.valid = (uint32_t)std::min<uint64_t>(tile, z.shard_len - off);
-            t.pad_ = 0;
-            off += tile;
-            if (off >= z.shard_len) {
-                off = 0;
-                ++si;
-            }
-        }
-        e = hipMemcpyAsync(ring->dev_tiles[slot], rec, nt * sizeof(hbec::TileRec), hipMemcpyHostToDevice,
-                           ring->s_cmp);
+    rc = walk_slots(ring, "zero-copy slot wait", "zero-copy event", [&](int slot, bool& more) -> int {
+        Rec* rec = reinterpret_cast<Rec*>(ring->pin_tiles[slot]);
+        cut::SlotFill f;
+        int frc = HBEC_OK;
+        const char* refused = nullptr;
+        auto flush = [&] { return (frc = ac.flush()) == HBEC_OK; };
+        if (!ps.d_digest) f = cut::fill_plain(recs, zs, si, off, rec, ring->tile_cap);
+        else refused = cut::fill_md5(recs, zs, si, rec, ring->tile_cap, ring->arena_cap, ps, ac, flush, f);
+        if (frc || refused) return frc ? frc : fail(HBEC_ERR_INVALID_ARG, refused);
+        more = si < zs.size();
+        hipError_t e = hipMemcpyAsync(ring->dev_tiles[slot], rec, (f.n_main + f.n_edge) * sizeof(Rec),
+                                      hipMemcpyHostToDevice, ring->s_cmp);
         if (e != hipSuccess) return hip_fail(e, "zero-copy records H2D");
         g_zc_record_slots.fetch_add(1, std::memory_order_relaxed);
-        int rc = hbec::launch_stripe_passes(ring->dev_tiles[slot], nt, in_idx, out_idx, rows, 0, ring->s_cmp,
-                                            zero_copy_blocks_per_cu(), false, zero_copy_max_blocks());
-        if (rc) return rc;
-        e = hipEventRecord(ring->ev_cmp[slot], ring->s_cmp);
-        if (e != hipSuccess) return hip_fail(e, "zero-copy event");
-    }
-    e = hipStreamSynchronize(ring->s_cmp);
-    if (e != hipSuccess) return hip_fail(e, "zero-copy drain");
-    return HBEC_OK;
+        return launch(reinterpret_cast<const Rec*>(ring->dev_tiles[slot]), f);
+    });
+    if (!rc && ps.d_digest) rc = ac.finish();
+    if (rc) return rc;
+    const hipError_t e = hipStreamSynchronize(ring->s_cmp);
+    return e != hipSuccess ? hip_fail(e, "zero-copy drain") : HBEC_OK;
 }
 
-// Pinned stripes at any alignment / shard length (S % 16 != 0 for most object
-// sizes): the same in-place PCIe coding through gf_apply_unaligned_plan
-// records (URec and TileRec are both 32 B, so the slot buffers are shared).
-int zero_copy_unaligned_run(Ring* ring, const std::vector<ZcStripe>& zs, const std::vector<int>& in_idx,
-                            const std::vector<int>& out_idx, const std::vector<uint8_t>& rows) {
-    static_assert(sizeof(hbec::URec) == sizeof(hbec::TileRec), "record slots are shared");
-    const uint64_t tile = hbec::urec_tile_for(std::min((int)in_idx.size(), hbec::kOddMaxK), false);
-    size_t si = 0;
-    uint64_t off = 0;
-    hipError_t e = hipSuccess;
-    for (int c = 0; si < zs.size(); ++c) {
-        const int slot = c % kSlots;
-        e = hipEventSynchronize(ring->ev_cmp[slot]);  // the slot's previous records are consumed
-        if (e != hipSuccess) return hip_fail(e, "zero-copy slot wait");
-        hbec::URec* rec = reinterpret_cast<hbec::URec*>(ring->pin_tiles[slot]);
-        uint64_t nt = 0;
-        std::vector<hbec::URec> edges;  // gf_odd: one per stripe started in this slot, after the main records
-        while (si < zs.size() && nt + edges.size() + 1 < ring->tile_cap) {
-            const ZcStripe& z = zs[si];
-            const uint64_t span = hbec::urec_span(z.shard_len);
-            if (off == 0 && hbec::odd_enabled()) edges.push_back({z.dev, 0, z.shard_len, 0});
-            if (off < span) rec[nt++] = {z.dev, 0, z.shard_len, off};
-            off += tile;
-            if (off >= span) {
-                off = 0;
-                ++si;
-            }
-        }
-        std::copy(edges.begin(), edges.end(), rec + nt);
-        e = hipMemcpyAsync(ring->dev_tiles[slot], rec, (nt + edges.size()) * sizeof(hbec::URec), hipMemcpyHostToDevice,
-                           ring->s_cmp);
-        if (e != hipSuccess) return hip_fail(e, "zero-copy records H2D");
-        g_zc_record_slots.fetch_add(1, std::memory_order_relaxed);
-        const hbec::URec* d_rec = reinterpret_cast<const hbec::URec*>(ring->dev_tiles[slot]);
-        int rc = hbec::launch_unaligned_passes(d_rec, nt, in_idx, out_idx, rows, 0, ring->s_cmp, zero_copy_max_blocks(),
-                                               d_rec + nt, edges.size());
-        if (rc) return rc;
-        e = hipEventRecord(ring->ev_cmp[slot], ring->s_cmp);
-        if (e != hipSuccess) return hip_fail(e, "zero-copy event");
-    }
-    e = hipStreamSynchronize(ring->s_cmp);
-    if (e != hipSuccess) return hip_fail(e, "zero-copy drain");
-    return HBEC_OK;
+// 16-B aligned stripes of S % 16 == 0: the stripes kernel (hashing: StripeArgs::mirror)
+int zero_copy_aligned(Ring* ring, const std::vector<ZcStripe>& zs, const Pass& ps) {
+    const cut::TileRecs recs{(uint64_t)hbec::stripes_tile_bytes(std::min((int)ps.in_idx.size(), hbec::kStripeMaxK))};
+    return zero_copy_run(ring, recs, zs, ps, [&](const hbec::TileRec* d_rec, const cut::SlotFill& f) {
+        return hbec::launch_stripe_passes(d_rec, f.n_main, ps.in_idx, ps.out_idx, ps.rows, 0, ring->s_cmp,
+                                          zero_copy_blocks_per_cu(), ps.d_digest != nullptr, zero_copy_max_blocks());
+    });
 }
 
-// Zero-copy with ShardHash (hbec_encode_host_md5 when every stripe is pinned):
-// the stripes kernel codes each stripe in place over PCIe, exactly as
-// zero_copy_run, and also writes every shard column it holds (inputs and
-// outputs) to a device hash arena (StripeArgs::mirror), so nothing crosses
-// PCIe twice and no CPU copy runs.  A full arena is hashed by one md5_list
-// launch on its own stream while the stripes kernel fills the next ones.
-// Stripe s's shard i lands at arena + its offset + i*S; its digest at
-// (s * n_shards + i) * 16 of d_digest.
-int zero_copy_md5_run(Ring* ring, const std::vector<ZcStripe>& zs, const std::vector<int>& in_idx,
-                      const std::vector<int>& out_idx, const std::vector<uint8_t>& rows, uint8_t* d_digest,
-                      int n_shards) {
-    const int K = (int)in_idx.size(), R = (int)out_idx.size();
-    int rc = ring_md5_init(*ring);
-    if (rc) return rc;
-    const uint64_t tile = (uint64_t)hbec::stripes_tile_bytes(std::min(K, hbec::kStripeMaxK));
-    ArenaCursor ac{ring, ring->s_cmp, d_digest};
-    hipError_t e = hipSuccess;
-    size_t si = 0;
-    for (int c = 0; si < zs.size(); ++c) {
-        const int slot = c % kSlots;
-        e = hipEventSynchronize(ring->ev_cmp[slot]);  // the slot's previous records are consumed
-        if (e != hipSuccess) return hip_fail(e, "zero-copy slot wait");
-        hbec::TileRec* rec = ring->pin_tiles[slot];
-        uint64_t nt = 0;
-        while (si < zs.size()) {
-            const ZcStripe& z = zs[si];
-            const uint64_t S = z.shard_len;
-            const uint64_t tiles = (S + tile - 1) / tile;
-            const uint64_t bytes = ((uint64_t)n_shards * S + 255) & ~uint64_t(255);
-            if (tiles > ring->tile_cap || bytes > ring->arena_cap)
-                return fail(HBEC_ERR_INVALID_ARG, "stripe too large for a hash arena");
-            if (nt > 0 && nt + tiles > ring->tile_cap) break;
-            if (!ac.fits(bytes, (uint64_t)(K + R))) {
-                if (nt > 0) break;  // launch this chunk first: the arena is hashed after its kernels
-                rc = ac.flush();
-                if (rc) return rc;
-            }
-            const uint64_t mbase = ac.base();
-            for (uint64_t off = 0; off < S; off += tile) {
-                hbec::TileRec& t = rec[nt++];
-                t.in_addr = z.dev + off;
-                t.out_addr = mbase + off;
-                t.in_stride = t.out_stride = (uint32_t)S;
-                t.valid = (uint32_t)std::min<uint64_t>(tile, S - off);
-                t.pad_ = 0;
-            }
-            for (int i : in_idx) ac.add(mbase + (uint64_t)i * S, S, (uint64_t)si * (uint64_t)n_shards + (uint64_t)i);
-            for (int i : out_idx) ac.add(mbase + (uint64_t)i * S, S, (uint64_t)si * (uint64_t)n_shards + (uint64_t)i);
-            ac.used += bytes;
-            ++si;
-        }
-        e = hipMemcpyAsync(ring->dev_tiles[slot], rec, nt * sizeof(hbec::TileRec), hipMemcpyHostToDevice,
-                           ring->s_cmp);
-        if (e != hipSuccess) return hip_fail(e, "zero-copy records H2D");
-        g_zc_record_slots.fetch_add(1, std::memory_order_relaxed);
-        rc = hbec::launch_stripe_passes(ring->dev_tiles[slot], nt, in_idx, out_idx, rows, 0, ring->s_cmp,
-                                        zero_copy_blocks_per_cu(), true, zero_copy_max_blocks());
-        if (rc) return rc;
-        e = hipEventRecord(ring->ev_cmp[slot], ring->s_cmp);
-        if (e != hipSuccess) return hip_fail(e, "zero-copy event");
-    }
-    rc = ac.finish();
-    if (rc) return rc;
-    e = hipStreamSynchronize(ring->s_cmp);
-    if (e != hipSuccess) return hip_fail(e, "zero-copy drain");
-    return HBEC_OK;
-}
-
-// Zero-copy with ShardHash for pinned stripes at any alignment / shard length
-// (15 object sizes in 16: ecSplit's S = ceil(len / k)): the mirrored gf_odd
-// plan kernel codes each stripe in place over PCIe, as
-// zero_copy_unaligned_run, and stores every shard column it holds to the
-// stripe's hash arena, where shard i sits 16-B aligned at arena + i * P
-// (P = odd_mirror_pitch_host(S)); gf_odd_mirror_copy adds the guard-band
-// bytes (<= 160 per shard) afterwards.  The arena is then hashed by md5_list
-// exactly as in zero_copy_md5_run.
-int zero_copy_unaligned_md5_run(Ring* ring, const std::vector<ZcStripe>& zs, const std::vector<int>& in_idx,
-                                const std::vector<int>& out_idx, const std::vector<uint8_t>& rows, uint8_t* d_digest,
-                                int n_shards) {
-    static_assert(sizeof(hbec::URec) == sizeof(hbec::TileRec), "record slots are shared");
-    const int K = (int)in_idx.size(), R = (int)out_idx.size();
-    int rc = ring_md5_init(*ring);
-    if (rc) return rc;
-    const uint64_t tile = hbec::urec_tile_for(std::min(K, hbec::kOddMaxK), true);
-    ArenaCursor ac{ring, ring->s_cmp, d_digest};
-    hipError_t e = hipSuccess;
-    size_t si = 0;
-    for (int c = 0; si < zs.size(); ++c) {
-        const int slot = c % kSlots;
-        e = hipEventSynchronize(ring->ev_cmp[slot]);  // the slot's previous records are consumed
-        if (e != hipSuccess) return hip_fail(e, "zero-copy slot wait");
-        hbec::URec* rec = reinterpret_cast<hbec::URec*>(ring->pin_tiles[slot]);
-        uint64_t nt = 0;
-        std::vector<hbec::URec> edges;  // one per stripe of this slot, after the main records
-        while (si < zs.size()) {
-            const ZcStripe& z = zs[si];
-            const uint64_t S = z.shard_len;
-            const uint64_t span = hbec::urec_span(S);
-            const uint64_t tiles = (span + tile - 1) / tile;
-            const uint64_t bytes = ((uint64_t)n_shards * hbec::odd_mirror_pitch_host(S) + 255) & ~uint64_t(255);
-            if (tiles + 2 > ring->tile_cap || bytes > ring->arena_cap)
-                return fail(HBEC_ERR_INVALID_ARG, "stripe too large for a hash arena");
-            // a stripe of S <= 160 adds an edge record and no main record, so
-            // the slot is full when main + edge records would pass tile_cap,
-            // whether or not a main record exists yet
-            const bool any = nt > 0 || !edges.empty();
-            if (any && nt + edges.size() + tiles + 1 > ring->tile_cap) break;
-            if (!ac.fits(bytes, (uint64_t)(K + R))) {
-                if (any) break;  // launch this chunk first: the arena is hashed after its kernels
-                rc = ac.flush();
-                if (rc) return rc;
-            }
-            const uint64_t mbase = ac.base();  // 256-B aligned
-            for (uint64_t off = 0; off < span; off += tile) rec[nt++] = {z.dev, mbase, S, off};
-            edges.push_back({z.dev, mbase, S, 0});
-            const uint64_t P = hbec::odd_mirror_pitch_host(S);
-            for (int i : in_idx) ac.add(mbase + (uint64_t)i * P, S, (uint64_t)si * (uint64_t)n_shards + (uint64_t)i);
-            for (int i : out_idx) ac.add(mbase + (uint64_t)i * P, S, (uint64_t)si * (uint64_t)n_shards + (uint64_t)i);
-            ac.used += bytes;
-            ++si;
-        }
-        std::copy(edges.begin(), edges.end(), rec + nt);
-        e = hipMemcpyAsync(ring->dev_tiles[slot], rec, (nt + edges.size()) * sizeof(hbec::URec), hipMemcpyHostToDevice,
-                           ring->s_cmp);
-        if (e != hipSuccess) return hip_fail(e, "zero-copy records H2D");
-        g_zc_record_slots.fetch_add(1, std::memory_order_relaxed);
-        const hbec::URec* d_rec = reinterpret_cast<const hbec::URec*>(ring->dev_tiles[slot]);
-        rc = hbec::launch_unaligned_passes(d_rec, nt, in_idx, out_idx, rows, 0, ring->s_cmp, zero_copy_max_blocks(),
-                                           d_rec + nt, edges.size(), true);
-        if (rc) return rc;
-        e = hipEventRecord(ring->ev_cmp[slot], ring->s_cmp);
-        if (e != hipSuccess) return hip_fail(e, "zero-copy event");
-    }
-    rc = ac.finish();
-    if (rc) return rc;
-    e = hipStreamSynchronize(ring->s_cmp);
-    if (e != hipSuccess) return hip_fail(e, "zero-copy drain");
-    return HBEC_OK;
+// Any alignment / shard length (15 object sizes in 16: ecSplit's S = ceil(len / k)):
+// gf_apply_unaligned_plan records.  Hashing: the mirrored gf_odd plan kernel stores
+// shard i 16-B aligned at arena + i * odd_mirror_pitch_host(S); gf_odd_mirror_copy
+// adds the guard-band bytes (<= 160 per shard) afterwards.
+int zero_copy_unaligned(Ring* ring, const std::vector<ZcStripe>& zs, const Pass& ps) {
+    const bool mirror = ps.d_digest != nullptr;
+    const cut::URecs recs{hbec::urec_tile_for(std::min((int)ps.in_idx.size(), hbec::kOddMaxK), mirror), hbec::urec_span,
+                          hbec::odd_mirror_pitch_host, hbec::odd_enabled()};
+    return zero_copy_run(ring, recs, zs, ps, [&](const hbec::URec* d_rec, const cut::SlotFill& f) {
+        return hbec::launch_unaligned_passes(d_rec, f.n_main, ps.in_idx, ps.out_idx, ps.rows, 0, ring->s_cmp,
+                                             zero_copy_max_blocks(), d_rec + f.n_main, f.n_edge, mirror);
+    });
 }
 
 std::atomic<uint64_t> g_md5_zc_calls{0}, g_md5_ring_calls{0};
@@ -670,274 +518,189 @@ bool zero_copy_md5_enabled() {
     return on;
 }
 
-// Code every stripe: inputs = shards in_idx, outputs = shards out_idx with `rows`.
-// With d_digest (device, n * n_shards * 16 B), also hash every input and
-// output shard of every stripe while it is in the device slot: digest of
-// shard i of stripe s at (s * n_shards + i) * 16.
-int host_run_on(Ring* ring, const hbec_stripe* stripes, uint64_t n, const std::vector<int>& in_idx,
-                const std::vector<int>& out_idx, const std::vector<uint8_t>& rows, uint8_t* d_digest,
-                int n_shards);
-
 // A call that fails part-way may leave work queued on the ring's streams
 // (slot copies, kernels writing a hash arena, hashes); the next caller of
 // the ring reuses slots only after their events, but starts over at hash
 // arena 0, so a failed call drains every stream before the ring goes back.
 void ring_drain(Ring* r) {
-    hipStream_t all[4 + Ring::kArenas] = {r->s_h2d, r->s_cmp, r->s_d2h};
-    int n = 3;
-    for (int a = 0; a < Ring::kArenas; ++a) all[n++] = r->s_md5[a];
-    for (int i = 0; i < n; ++i)
-        if (all[i]) (void)hipStreamSynchronize(all[i]);
+    for (hipStream_t s : {r->s_h2d, r->s_cmp, r->s_d2h})
+        if (s) (void)hipStreamSynchronize(s);
+    for (hipStream_t s : r->s_md5)
+        if (s) (void)hipStreamSynchronize(s);
     (void)hipGetLastError();
 }
 
-int host_run(const hbec_stripe* stripes, uint64_t n, const std::vector<int>& in_idx,
-             const std::vector<int>& out_idx, const std::vector<uint8_t>& rows, uint8_t* d_digest = nullptr,
-             int n_shards = 0) {
-    if (out_idx.empty() || n == 0) return HBEC_OK;
+// A ring of the calling thread's device for the length of fn(ring).
+template <class Fn>
+int with_ring(Fn fn) {
     Ring* ring = nullptr;
     int rc = ring_acquire(&ring);
     if (rc) return rc;
-    struct Releaser {
+    struct Back {
         Ring* r;
-        bool ok = false;
-        ~Releaser() {
-            if (!ok) ring_drain(r);
+        bool ok;
+        ~Back() {
+            if (!ok) ring_drain(r);  // also when fn threw
             ring_release(r);
         }
-    } rel{ring};
-    rc = host_run_on(ring, stripes, n, in_idx, out_idx, rows, d_digest, n_shards);
-    rel.ok = rc == HBEC_OK;
+    } back{ring, false};
+    rc = fn(ring);
+    back.ok = rc == HBEC_OK;
     return rc;
 }
 
-int host_run_on(Ring* ring, const hbec_stripe* stripes, uint64_t n, const std::vector<int>& in_idx,
-                const std::vector<int>& out_idx, const std::vector<uint8_t>& rows, uint8_t* d_digest,
-                int n_shards) {
-    const int K = (int)in_idx.size(), R = (int)out_idx.size();
-    int rc = HBEC_OK;
-    // Pinned stripes are coded in place (zero-copy); the rest take the ring.
-    // Hashing needs every shard on the device: when every stripe is pinned,
-    // the zero-copy kernel also copies them to a device hash arena
-    // (zero_copy_md5_run); otherwise the whole batch takes the ring.
-    if (d_digest && zero_copy_enabled() && zero_copy_md5_enabled()) {
-        int top = 0;
-        for (int i : in_idx) top = std::max(top, i);
-        for (int i : out_idx) top = std::max(top, i);
-        std::vector<ZcStripe> zs;
-        zs.reserve(n);
-        // every stripe pinned: the aligned mirror kernel when all are 16-B
-        // aligned with S % 16 == 0, else the mirrored gf_odd plan for all
-        const bool any_align = hbec::zero_copy_any_alignment() && hbec::odd_enabled();
-        bool all_aligned = true;
-        for (uint64_t s = 0; s < n; ++s) {
-            const uint64_t S = stripes[s].shard_len;
-            if (!stripes[s].base || S == 0) break;
-            const bool aligned = (reinterpret_cast<uintptr_t>(stripes[s].base) & 15u) == 0 && S % 16 == 0 &&
-                                 S < (1ull << 32);
-            if (!aligned && (!any_align || !hbec::pos32_shard(S))) break;
-            const uint64_t d = pinned_device_addr(stripes[s].base, (uint64_t)(top + 1) * S);
-            if (!d) break;
-            all_aligned = all_aligned && aligned && (d & 15u) == 0;
-            zs.push_back({d, S});
-        }
-        if (zs.size() == n && !all_aligned && !any_align) zs.clear();
-        if (zs.size() == n && !all_aligned) {
-            const uint64_t max_cols = (std::min(ring->in_cap / in_idx.size(), ring->out_cap / out_idx.size()) / 16) * 16;
-            for (const ZcStripe& z : zs)
-                if (z.shard_len > max_cols)
-                    return fail(HBEC_ERR_INVALID_ARG, "hashing needs every stripe to fit one staging slot");
-            g_md5_zc_calls.fetch_add(1, std::memory_order_relaxed);
-            return zero_copy_unaligned_md5_run(ring, zs, in_idx, out_idx, rows, d_digest, n_shards);
-        }
-        if (zs.size() == n) {
-            // the same stripe bound as the ring (hbec.h: one staging slot)
-            const uint64_t max_cols = (std::min(ring->in_cap / in_idx.size(), ring->out_cap / out_idx.size()) / 16) * 16;
-            for (const ZcStripe& z : zs)
-                if (z.shard_len > max_cols)
-                    return fail(HBEC_ERR_INVALID_ARG, "hashing needs every stripe to fit one staging slot");
-            g_md5_zc_calls.fetch_add(1, std::memory_order_relaxed);
-            return zero_copy_md5_run(ring, zs, in_idx, out_idx, rows, d_digest, n_shards);
-        }
-    }
-    if (d_digest) g_md5_ring_calls.fetch_add(1, std::memory_order_relaxed);
-    std::vector<hbec_stripe> staged;
-    if (!d_digest && zero_copy_enabled()) {
-        int top = 0;
-        for (int i : in_idx) top = std::max(top, i);
-        for (int i : out_idx) top = std::max(top, i);
-        std::vector<ZcStripe> zs, zu;  // aligned (stripes kernel) / any alignment (unaligned kernel)
-        for (uint64_t s = 0; s < n; ++s) {
-            const uint64_t S = stripes[s].shard_len;
-            if (S == 0) continue;
-            const uint64_t d = stripes[s].base ? pinned_device_addr(stripes[s].base, (uint64_t)(top + 1) * S) : 0;
-            const bool aligned = (reinterpret_cast<uintptr_t>(stripes[s].base) & 15u) == 0 && S % 16 == 0 &&
-                                 S < (1ull << 32) && (d & 15u) == 0;
-            if (d && aligned) zs.push_back({d, S});
-            else if (d && hbec::zero_copy_any_alignment() && hbec::pos32_shard(S)) zu.push_back({d, S});  // gf_odd: 32-bit positions
-            else staged.push_back(stripes[s]);
-        }
-        if (!zs.empty()) {
-            rc = zero_copy_run(ring, zs, in_idx, out_idx, rows);
-            if (rc) return rc;
-        }
-        if (!zu.empty()) {
-            rc = zero_copy_unaligned_run(ring, zu, in_idx, out_idx, rows);
-            if (rc) return rc;
-        }
-        if (staged.empty()) return HBEC_OK;
-        stripes = staged.data();
-        n = staged.size();
-    }
-    rc = ring_staging_init(*ring);
-    if (rc) return rc;
-    const uint64_t tile = (uint64_t)hbec::stripes_tile_bytes(std::min(K, hbec::kStripeMaxK));
-    // max columns per piece so that K*lpad fits the IN slot and R*lpad the OUT slot
-    const uint64_t max_cols = (std::min(ring->in_cap / K, ring->out_cap / R) / 16) * 16;
-    if (max_cols < 16) return fail(HBEC_ERR_INVALID_ARG, "staging slot too small");
-    if (d_digest) {
-        for (uint64_t s = 0; s < n; ++s)
-            if (stripes[s].shard_len > max_cols)
-                return fail(HBEC_ERR_INVALID_ARG, "hashing needs every stripe to fit one staging slot");
-        rc = ring_md5_init(*ring);
+using Pieces = std::vector<cut::Piece>;
+
+// The CPU copies of a chunk (thread pool): gather shards idx of the pieces into
+// the pinned IN slot, packed 0.. per piece and zero-padded to lpad, or hand the
+// pinned OUT slot's shards, packed likewise, back to the caller's stripes.
+void ring_copy(Ring* ring, int slot, const Pieces& pieces, const hbec_stripe* stripes, const std::vector<int>& idx,
+               bool gather) {
+    const size_t n = idx.size();
+    ring->pool->parallel_for(pieces.size() * n, [&](size_t i) {
+        const cut::Piece& p = pieces[i / n];
+        const size_t j = i % n;
+        const hbec_stripe& st = stripes[p.stripe];
+        uint8_t* mem = static_cast<uint8_t*>(st.base) + (uint64_t)idx[j] * st.shard_len + p.col;
+        uint8_t* pin = (gather ? ring->pin_in[slot] + p.in_off : ring->pin_out[slot] + p.out_off) + j * p.lpad;
+        std::memcpy(gather ? pin : mem, gather ? mem : pin, p.len);
+        if (gather && p.lpad > p.len) std::memset(pin + p.len, 0, p.lpad - p.len);
+    });
+}
+
+// the chunk's shards -> hash arena (D2D on the compute stream, before the slot is released)
+int ring_hash_chunk(ArenaCursor& ac, int slot, const Pieces& pieces, uint64_t in_bytes, uint64_t out_bytes,
+                    const Pass& ps) {
+    Ring* ring = ac.ring;
+    const size_t K = ps.in_idx.size(), R = ps.out_idx.size();
+    if (!ac.fits(in_bytes + out_bytes, pieces.size() * (uint64_t)(K + R))) {
+        const int rc = ac.flush();
         if (rc) return rc;
     }
-    ArenaCursor ac{ring, ring->s_cmp, d_digest};  // hash arenas (d_digest only)
-
-    // Cut the batch into chunks of pieces that fit a slot.
-    std::vector<std::vector<Piece>> chunks(1);
-    uint64_t in_used = 0, out_used = 0, tiles_used = 0;
-    for (uint64_t s = 0; s < n; ++s) {
-        const uint64_t S = stripes[s].shard_len;
-        if (S == 0) continue;
-        if (!stripes[s].base) return fail(HBEC_ERR_INVALID_ARG, "stripe with null base");
-        for (uint64_t col = 0; col < S; col += max_cols) {
-            Piece p;
-            p.stripe = s;
-            p.col = col;
-            p.len = std::min(max_cols, S - col);
-            p.lpad = (p.len + 15) / 16 * 16;
-            const uint64_t nt = (p.lpad + tile - 1) / tile;
-            if (in_used + K * p.lpad > ring->in_cap || out_used + R * p.lpad > ring->out_cap ||
-                tiles_used + nt > ring->tile_cap) {
-                chunks.emplace_back();
-                in_used = out_used = tiles_used = 0;
-            }
-            p.in_off = in_used;
-            p.out_off = out_used;
-            in_used += K * p.lpad;
-            out_used += R * p.lpad;
-            tiles_used += nt;
-            chunks.back().push_back(p);
-            g_ring_pieces.fetch_add(1, std::memory_order_relaxed);
-        }
+    const uint64_t ain = ac.base(), aout = ain + in_bytes;
+    hipError_t e = hipMemcpyAsync(reinterpret_cast<void*>(ain), ring->dev_in[slot], in_bytes, hipMemcpyDeviceToDevice,
+                                  ring->s_cmp);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(reinterpret_cast<void*>(aout), ring->dev_out[slot], out_bytes, hipMemcpyDeviceToDevice,
+                           ring->s_cmp);
+    if (e != hipSuccess) return hip_fail(e, "hash arena copy");
+    const uint64_t n_shards = (uint64_t)ps.n_shards;
+    for (const cut::Piece& p : pieces) {
+        for (size_t j = 0; j < K; ++j)
+            ac.add(ain + p.in_off + (uint64_t)j * p.lpad, p.len, p.stripe * n_shards + (uint64_t)ps.in_idx[j]);
+        for (size_t r = 0; r < R; ++r)
+            ac.add(aout + p.out_off + (uint64_t)r * p.lpad, p.len, p.stripe * n_shards + (uint64_t)ps.out_idx[r]);
     }
-    if (chunks.back().empty()) chunks.pop_back();
+    ac.used += (in_bytes + out_bytes + 255) & ~uint64_t(255);
+    return HBEC_OK;
+}
+
+// The staging ring: chunks of column pieces through kSlots slots, each gathered, uploaded, coded,
+// with d_digest copied to a hash arena, downloaded, and scattered when its slot comes round again.
+int ring_run(Ring* ring, const hbec_stripe* stripes, uint64_t n, const Pass& ps) {
+    const int K = (int)ps.in_idx.size(), R = (int)ps.out_idx.size();
+    int rc = ring_staging_init(*ring);
+    if (rc) return rc;
+    const uint64_t tile = (uint64_t)hbec::stripes_tile_bytes(std::min(K, hbec::kStripeMaxK));
+    std::vector<Pieces> chunks;
+    uint64_t n_pieces = 0;
+    const char* refused = cut::cut_ring(stripes, n, K, R, ring->in_cap, ring->out_cap, ring->tile_cap, tile,
+                                        ps.d_digest != nullptr, chunks, n_pieces);
+    g_ring_pieces.fetch_add(n_pieces, std::memory_order_relaxed);
+    if (refused) return fail(HBEC_ERR_INVALID_ARG, refused);
+    rc = ps.d_digest ? ring_md5_init(*ring) : HBEC_OK;
+    if (rc) return rc;
+    ArenaCursor ac{ring, ring->s_cmp, ps.d_digest};  // hash arenas (d_digest only)
 
     // in the slots inputs are packed 0..K-1 and outputs 0..R-1
     std::vector<int> slot_in(K), slot_out(R);
     for (int j = 0; j < K; ++j) slot_in[j] = j;
     for (int r = 0; r < R; ++r) slot_out[r] = r;
 
-    std::vector<int64_t> slot_chunk(kSlots, -1);
-    auto scatter = [&](int slot) -> int {
-        const int64_t c = slot_chunk[slot];
-        if (c < 0) return HBEC_OK;
-        hipError_t e = hipEventSynchronize(ring->ev_done[slot]);
-        if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize");
-        const auto& pieces = chunks[c];
-        ring->pool->parallel_for(pieces.size() * R, [&](size_t i) {
-            const Piece& p = pieces[i / R];
-            const int r = (int)(i % R);
-            const hbec_stripe& st = stripes[p.stripe];
-            std::memcpy(static_cast<uint8_t*>(st.base) + (uint64_t)out_idx[r] * st.shard_len + p.col,
-                        ring->pin_out[slot] + p.out_off + (uint64_t)r * p.lpad, p.len);
-        });
-        slot_chunk[slot] = -1;
-        return HBEC_OK;
-    };
-
-    for (size_t c = 0; c < chunks.size(); ++c) {
+    // chunk c's slot is free once chunk c - kSlots is back in the caller's memory; the
+    // last kSlots chunks are handed back by the turns past the end
+    for (size_t c = 0; c < chunks.size() + kSlots; ++c) {
         const int slot = (int)(c % kSlots);
-        rc = scatter(slot);  // the slot's previous chunk is complete; hand its output back
-        if (rc) return rc;
-        const auto& pieces = chunks[c];
-        // gather inputs into the pinned IN slot and build the tile records
-        ring->pool->parallel_for(pieces.size() * K, [&](size_t i) {
-            const Piece& p = pieces[i / K];
-            const int j = (int)(i % K);
-            const hbec_stripe& st = stripes[p.stripe];
-            uint8_t* dst = ring->pin_in[slot] + p.in_off + (uint64_t)j * p.lpad;
-            std::memcpy(dst, static_cast<const uint8_t*>(st.base) + (uint64_t)in_idx[j] * st.shard_len + p.col,
-                        p.len);
-            if (p.lpad > p.len) std::memset(dst + p.len, 0, p.lpad - p.len);
-        });
+        if (c >= kSlots) {
+            hipError_t e = hipEventSynchronize(ring->ev_done[slot]);
+            if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize");
+            ring_copy(ring, slot, chunks[c - kSlots], stripes, ps.out_idx, false);
+        }
+        if (c >= chunks.size()) continue;
+        const Pieces& pieces = chunks[c];
+        ring_copy(ring, slot, pieces, stripes, ps.in_idx, true);
         uint64_t nt = 0, in_bytes = 0, out_bytes = 0;
         const uint64_t din = reinterpret_cast<uint64_t>(ring->dev_in[slot]);
         const uint64_t dout = reinterpret_cast<uint64_t>(ring->dev_out[slot]);
-        for (const Piece& p : pieces) {
-            for (uint64_t off = 0; off < p.lpad; off += tile) {
-                hbec::TileRec& t = ring->pin_tiles[slot][nt++];
-                t.in_addr = din + p.in_off + off;
-                t.out_addr = dout + p.out_off + off;
-                t.in_stride = (uint32_t)p.lpad;
-                t.out_stride = (uint32_t)p.lpad;
-                t.valid = (uint32_t)std::min<uint64_t>(tile, p.lpad - off);
-                t.pad_ = 0;
-            }
+        for (const cut::Piece& p : pieces) {
+            for (uint64_t off = 0; off < p.lpad; off += tile)
+                ring->pin_tiles[slot][nt++] = cut::tile_rec(din + p.in_off, dout + p.out_off, p.lpad, off, p.lpad, tile);
             in_bytes = std::max(in_bytes, p.in_off + K * p.lpad);
             out_bytes = std::max(out_bytes, p.out_off + R * p.lpad);
         }
-        hipError_t e = hipSuccess;
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(ring->dev_tiles[slot], ring->pin_tiles[slot], nt * sizeof(hbec::TileRec),
-                               hipMemcpyHostToDevice, ring->s_h2d);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(ring->dev_in[slot], ring->pin_in[slot], in_bytes, hipMemcpyHostToDevice, ring->s_h2d);
-        if (e == hipSuccess) e = hipEventRecord(ring->ev_h2d[slot], ring->s_h2d);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ring->s_cmp, ring->ev_h2d[slot], 0);
-        if (e != hipSuccess) return hip_fail(e, "host path H2D");
-        rc = hbec::launch_stripe_passes(ring->dev_tiles[slot], nt, slot_in, slot_out, rows, 0, ring->s_cmp);
+        rc = staged_upload(ring, slot, nt * sizeof(hbec::TileRec), in_bytes, "host path H2D");
+        if (!rc) rc = hbec::launch_stripe_passes(ring->dev_tiles[slot], nt, slot_in, slot_out, ps.rows, 0, ring->s_cmp);
+        if (!rc && ps.d_digest) rc = ring_hash_chunk(ac, slot, pieces, in_bytes, out_bytes, ps);
         if (rc) return rc;
-        if (d_digest) {  // the chunk's shards -> hash arena (D2D, same stream, before the slot is released)
-            if (!ac.fits(in_bytes + out_bytes, pieces.size() * (uint64_t)(K + R))) {
-                rc = ac.flush();
-                if (rc) return rc;
-            }
-            const uint64_t ain = ac.base();
-            const uint64_t aout = ain + in_bytes;
-            e = hipMemcpyAsync(reinterpret_cast<void*>(ain), ring->dev_in[slot], in_bytes, hipMemcpyDeviceToDevice,
-                               ring->s_cmp);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(reinterpret_cast<void*>(aout), ring->dev_out[slot], out_bytes,
-                                   hipMemcpyDeviceToDevice, ring->s_cmp);
-            if (e != hipSuccess) return hip_fail(e, "hash arena copy");
-            for (const Piece& p : pieces) {
-                for (int j = 0; j < K; ++j)
-                    ac.add(ain + p.in_off + (uint64_t)j * p.lpad, p.len, p.stripe * (uint64_t)n_shards + (uint64_t)in_idx[j]);
-                for (int r = 0; r < R; ++r)
-                    ac.add(aout + p.out_off + (uint64_t)r * p.lpad, p.len,
-                           p.stripe * (uint64_t)n_shards + (uint64_t)out_idx[r]);
-            }
-            ac.used += (in_bytes + out_bytes + 255) & ~uint64_t(255);
-        }
-        e = hipEventRecord(ring->ev_cmp[slot], ring->s_cmp);
+        hipError_t e = hipEventRecord(ring->ev_cmp[slot], ring->s_cmp);
         if (e == hipSuccess) e = hipStreamWaitEvent(ring->s_d2h, ring->ev_cmp[slot], 0);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(ring->pin_out[slot], ring->dev_out[slot], out_bytes, hipMemcpyDeviceToHost,
-                               ring->s_d2h);
+            e = hipMemcpyAsync(ring->pin_out[slot], ring->dev_out[slot], out_bytes, hipMemcpyDeviceToHost, ring->s_d2h);
         if (e == hipSuccess) e = hipEventRecord(ring->ev_done[slot], ring->s_d2h);
         if (e != hipSuccess) return hip_fail(e, "host path D2H");
-        slot_chunk[slot] = (int64_t)c;
         g_ring_chunks.fetch_add(1, std::memory_order_relaxed);
     }
-    for (size_t i = 0; i < chunks.size() + kSlots; ++i) {  // drain in chunk order
-        const int slot = (int)(i % kSlots);
-        rc = scatter(slot);
-        if (rc) return rc;
+    return ps.d_digest ? ac.finish() : HBEC_OK;
+}
+
+// Code every stripe by pass ps (hostcut.h).  Pinned stripes are coded in place
+// (zero-copy); the rest take the ring.  Hashing needs every shard on the
+// device: when every stripe is pinned, the zero-copy kernel also copies them
+// to a device hash arena; otherwise the whole batch takes the ring.
+int host_run_on(Ring* ring, const hbec_stripe* stripes, uint64_t n, const Pass& ps) {
+    const int top = cut::top_shard(ps);
+    std::vector<ZcStripe> zs, zu;  // aligned (stripes kernel) / any alignment (unaligned kernel)
+    if (ps.d_digest && zero_copy_enabled() && zero_copy_md5_enabled()) {
+        // the mirrored gf_odd plan is the only unaligned kernel with a mirror
+        const bool any_align = hbec::zero_copy_any_alignment() && hbec::odd_enabled();
+        const cut::Kind all = cut::route_hashing(stripes, n, top, any_align, pinned_device_addr, zs);
+        if (all != cut::Kind::staged) {
+            // the same stripe bound as the ring (hbec.h: one staging slot)
+            const uint64_t max_cols =
+                cut::slot_cols(ring->in_cap, ring->out_cap, (int)ps.in_idx.size(), (int)ps.out_idx.size());
+            if (const char* refused = cut::hash_slot_bound(zs.data(), zs.size(), max_cols))
+                return fail(HBEC_ERR_INVALID_ARG, refused);
+            g_md5_zc_calls.fetch_add(1, std::memory_order_relaxed);
+            return all == cut::Kind::aligned ? zero_copy_aligned(ring, zs, ps) : zero_copy_unaligned(ring, zs, ps);
+        }
     }
-    if (d_digest) return ac.finish();
-    return HBEC_OK;
+    if (ps.d_digest) g_md5_ring_calls.fetch_add(1, std::memory_order_relaxed);
+    std::vector<hbec_stripe> staged;
+    if (!ps.d_digest && zero_copy_enabled()) {
+        cut::route_plain(stripes, n, top, hbec::zero_copy_any_alignment(), pinned_device_addr, zs, zu, staged);
+        int rc = zs.empty() ? HBEC_OK : zero_copy_aligned(ring, zs, ps);
+        if (!rc && !zu.empty()) rc = zero_copy_unaligned(ring, zu, ps);
+        if (rc || staged.empty()) return rc;
+        stripes = staged.data();
+        n = staged.size();
+    }
+    return ring_run(ring, stripes, n, ps);
+}
+
+int host_run(const hbec_stripe* stripes, uint64_t n, const Pass& ps) {
+    if (ps.out_idx.empty() || n == 0) return HBEC_OK;
+    return with_ring([&](Ring* ring) { return host_run_on(ring, stripes, n, ps); });
+}
+
+// The encode pass: data shards 0..k-1 in, parity shards k..k+m-1 out by the codec's parity rows.
+int encode_host_run(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n, uint8_t* d_digest = nullptr) {
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+    std::vector<uint8_t> mat((size_t)(k + m) * k);
+    hbec_matrix(codec, mat.data());
+    Pass ps{std::vector<int>(k), std::vector<int>(m), {mat.begin() + (size_t)k * k, mat.end()}, d_digest, k + m};
+    for (int j = 0; j < k; ++j) ps.in_idx[j] = j;
+    for (int r = 0; r < m; ++r) ps.out_idx[r] = k + r;
+    return host_run(stripes, n, ps);
 }
 
 // ---- Verify of host stripes (hbec_verify_host) ----
@@ -948,15 +711,61 @@ int host_run_on(Ring* ring, const hbec_stripe* stripes, uint64_t n, const std::v
 // same kernels over records of the device slot; a stripe larger than a slot
 // is cut into column pieces ((k+m) copies each) that OR into its flag.  A slot
 // is reused once the kernel that read it is done (ev_cmp).
-struct VPiece {
-    uint64_t stripe, col, len, off;  // off: the piece's (k+m) x len block in the slot
-    bool whole;                      // col == 0 and len == S: one copy
-};
+
+// queue the Verify of v: its records, already at d_rec (VRecs, then VTiles), and its other-route stripes;
+// without records d_rec may be null: verify_recs_run returns before it looks at it
+int verify_queue(hbec_codec* codec, const hbec::VerifyRecs& v, const void* d_rec, const uint32_t* d_tab,
+                 uint32_t* d_flags, hipStream_t st, int max_blocks = 0) {
+    const uint8_t* r = static_cast<const uint8_t*>(d_rec);
+    int rc = hbec::verify_recs_run(codec, reinterpret_cast<const hbec::VRec*>(r), v.recs.size(),
+                                   reinterpret_cast<const hbec::VTile*>(r + v.recs.size() * sizeof(hbec::VRec)),
+                                   v.tiles.size(), d_tab, d_flags, st, max_blocks);
+    for (size_t i = 0; i < v.other.size() && !rc; ++i) rc = hbec::verify_other_run(codec, v.other[i], d_flags, st);
+    return rc;
+}
+
+int verify_staged(Ring* ring, hbec_codec* codec, const hbec_stripe* stripes, const std::vector<uint64_t>& staged,
+                  const uint32_t* d_tab, uint32_t* d_flags) {
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+    const uint64_t L = (uint64_t)(k + m);
+    int rc = ring_staging_init(*ring);
+    if (rc) return rc;
+    std::vector<std::vector<cut::VPiece>> chunks;
+    if (const char* refused = cut::cut_verify(stripes, staged, L, ring->in_cap,
+                                              (uint64_t)ring->tile_cap * sizeof(hbec::TileRec), chunks))
+        return fail(HBEC_ERR_INVALID_ARG, refused);
+    size_t c = 0;
+    return walk_slots(ring, "verify host slot wait", "verify host event", [&](int slot, bool& more) -> int {
+        const auto& pieces = chunks[c++];
+        more = c < chunks.size();
+        ring->pool->parallel_for(pieces.size(), [&](size_t i) {
+            const cut::VPiece& p = pieces[i];
+            const uint8_t* src = static_cast<const uint8_t*>(stripes[p.stripe].base);
+            uint8_t* dst = ring->pin_in[slot] + p.off;
+            const uint64_t S = stripes[p.stripe].shard_len;
+            if (p.whole) std::memcpy(dst, src, L * p.len);
+            for (uint64_t j = 0; j < L && !p.whole; ++j) std::memcpy(dst + j * p.len, src + j * S + p.col, p.len);
+        });
+        const uint64_t din = reinterpret_cast<uint64_t>(ring->dev_in[slot]);
+        hbec::VerifyRecs vr;
+        uint64_t in_bytes = 0;
+        for (const cut::VPiece& p : pieces) {
+            (void)hbec::vp_add(vr, k, m, din + p.off, din + p.off + (uint64_t)k * p.len, p.len, p.stripe);
+            in_bytes = std::max(in_bytes, p.off + L * p.len);
+        }
+        const size_t rb = vr.recs.size() * sizeof(hbec::VRec), tb = vr.tiles.size() * sizeof(hbec::VTile);
+        uint8_t* prec = reinterpret_cast<uint8_t*>(ring->pin_tiles[slot]);
+        if (rb) std::memcpy(prec, vr.recs.data(), rb);
+        if (tb) std::memcpy(prec + rb, vr.tiles.data(), tb);
+        const int rc = staged_upload(ring, slot, rb + tb, in_bytes, "verify host H2D");
+        if (rc) return rc;
+        return verify_queue(codec, vr, ring->dev_tiles[slot], d_tab, d_flags, ring->s_cmp);
+    });
+}
 
 int verify_host_run_on(Ring* ring, hbec_codec* codec, const hbec_stripe* stripes, uint64_t n, uint8_t* flags) {
     const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
     const uint64_t L = (uint64_t)(k + m);
-    const bool fast = hbec::vp_fast_shape(k, m);
     hipStream_t st = ring->s_cmp;
     hbec::VerifyRecs zc;  // pinned stripes
     std::vector<uint64_t> staged;
@@ -970,7 +779,7 @@ int verify_host_run_on(Ring* ring, hbec_codec* codec, const hbec_stripe* stripes
     }
     // device flags, then the coefficient tables (stream-ordered scratch)
     std::vector<uint32_t> tab;
-    if (fast) hbec::verify_tab(codec, tab);
+    if (hbec::vp_fast_shape(k, m)) hbec::verify_tab(codec, tab);
     const size_t flag_bytes = ((size_t)n * 4 + 15) & ~(size_t)15;
     void* d_mem = nullptr;
     int rc = hbec::scratch_alloc(flag_bytes + tab.size() * 4, st, &d_mem);
@@ -988,8 +797,8 @@ int verify_host_run_on(Ring* ring, hbec_codec* codec, const hbec_stripe* stripes
     if (e == hipSuccess && !tab.empty()) e = hbec::launch_put_words(const_cast<uint32_t*>(d_tab), tab.data(), tab.size() * 4, st);
     if (e != hipSuccess) return hip_fail(e, "verify host flags");
 
+    void* d_rec = nullptr;
     if (!zc.recs.empty()) {
-        void* d_rec = nullptr;
         const size_t rb = zc.recs.size() * sizeof(hbec::VRec), tb = zc.tiles.size() * sizeof(hbec::VTile);
         rc = hbec::scratch_alloc(rb + tb, st, &d_rec);
         if (rc) return rc;
@@ -998,86 +807,13 @@ int verify_host_run_on(Ring* ring, hbec_codec* codec, const hbec_stripe* stripes
         if (e == hipSuccess && tb)
             e = hipMemcpyAsync(static_cast<uint8_t*>(d_rec) + rb, zc.tiles.data(), tb, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return hip_fail(e, "verify host records H2D");
-        rc = hbec::verify_recs_run(codec, static_cast<const hbec::VRec*>(d_rec), zc.recs.size(),
-                                   reinterpret_cast<const hbec::VTile*>(static_cast<uint8_t*>(d_rec) + rb),
-                                   zc.tiles.size(), d_tab, d_flags, st, zero_copy_max_blocks());
-        if (rc) return rc;
     }
-    for (const hbec::VOther& o : zc.other) {
-        rc = hbec::verify_other_run(codec, o, d_flags, st);
-        if (rc) return rc;
-    }
+    rc = verify_queue(codec, zc, d_rec, d_tab, d_flags, st, zero_copy_max_blocks());
+    if (rc) return rc;
 
     if (!staged.empty()) {
-        rc = ring_staging_init(*ring);
+        rc = verify_staged(ring, codec, stripes, staged, d_tab, d_flags);
         if (rc) return rc;
-        const uint64_t max_cols = (ring->in_cap / L / 16) * 16;
-        if (max_cols < 16) return fail(HBEC_ERR_INVALID_ARG, "staging slot too small");
-        const uint64_t rec_cap = (uint64_t)ring->tile_cap * sizeof(hbec::TileRec);
-        auto rec_bytes = [](uint64_t len) {
-            return sizeof(hbec::VRec) + (uint64_t)((hbec::vp_main_bytes((uint32_t)len) + hbec::kVpTile - 1) / hbec::kVpTile) *
-                                            sizeof(hbec::VTile);
-        };
-        std::vector<std::vector<VPiece>> chunks(1);
-        uint64_t used = 0, rused = 0;
-        for (uint64_t s : staged) {
-            const uint64_t S = stripes[s].shard_len;
-            const bool whole = L * S <= ring->in_cap;
-            for (uint64_t col = 0; col < S; col += whole ? S : max_cols) {
-                const uint64_t len = whole ? S : std::min(max_cols, S - col);
-                const uint64_t bytes = (L * len + 15) & ~(uint64_t)15, rb = rec_bytes(len);
-                if (used + bytes > ring->in_cap || rused + rb > rec_cap) {
-                    chunks.emplace_back();
-                    used = rused = 0;
-                }
-                chunks.back().push_back({s, col, len, used, whole});
-                used += bytes;
-                rused += rb;
-            }
-        }
-        for (size_t c = 0; c < chunks.size(); ++c) {
-            const int slot = (int)(c % kSlots);
-            e = hipEventSynchronize(ring->ev_cmp[slot]);  // the kernel that read this slot is done
-            if (e != hipSuccess) return hip_fail(e, "verify host slot wait");
-            const auto& pieces = chunks[c];
-            ring->pool->parallel_for(pieces.size(), [&](size_t i) {
-                const VPiece& p = pieces[i];
-                const uint8_t* src = static_cast<const uint8_t*>(stripes[p.stripe].base);
-                uint8_t* dst = ring->pin_in[slot] + p.off;
-                if (p.whole) {
-                    std::memcpy(dst, src, L * p.len);
-                    return;
-                }
-                const uint64_t S = stripes[p.stripe].shard_len;
-                for (uint64_t j = 0; j < L; ++j) std::memcpy(dst + j * p.len, src + j * S + p.col, p.len);
-            });
-            const uint64_t din = reinterpret_cast<uint64_t>(ring->dev_in[slot]);
-            hbec::VerifyRecs vr;
-            uint64_t in_bytes = 0;
-            for (const VPiece& p : pieces) {
-                (void)hbec::vp_add(vr, k, m, din + p.off, din + p.off + (uint64_t)k * p.len, p.len, p.stripe);
-                in_bytes = std::max(in_bytes, p.off + L * p.len);
-            }
-            const size_t rb = vr.recs.size() * sizeof(hbec::VRec), tb = vr.tiles.size() * sizeof(hbec::VTile);
-            uint8_t* prec = reinterpret_cast<uint8_t*>(ring->pin_tiles[slot]);
-            if (rb) std::memcpy(prec, vr.recs.data(), rb);
-            if (tb) std::memcpy(prec + rb, vr.tiles.data(), tb);
-            e = hipSuccess;
-            if (rb + tb) e = hipMemcpyAsync(ring->dev_tiles[slot], prec, rb + tb, hipMemcpyHostToDevice, ring->s_h2d);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(ring->dev_in[slot], ring->pin_in[slot], in_bytes, hipMemcpyHostToDevice, ring->s_h2d);
-            if (e == hipSuccess) e = hipEventRecord(ring->ev_h2d[slot], ring->s_h2d);
-            if (e == hipSuccess) e = hipStreamWaitEvent(st, ring->ev_h2d[slot], 0);
-            if (e != hipSuccess) return hip_fail(e, "verify host H2D");
-            const uint8_t* drec = reinterpret_cast<const uint8_t*>(ring->dev_tiles[slot]);
-            rc = hbec::verify_recs_run(codec, reinterpret_cast<const hbec::VRec*>(drec), vr.recs.size(),
-                                       reinterpret_cast<const hbec::VTile*>(drec + rb), vr.tiles.size(), d_tab, d_flags,
-                                       st);
-            for (size_t i = 0; i < vr.other.size() && !rc; ++i) rc = hbec::verify_other_run(codec, vr.other[i], d_flags, st);
-            if (rc) return rc;
-            e = hipEventRecord(ring->ev_cmp[slot], st);
-            if (e != hipSuccess) return hip_fail(e, "verify host event");
-        }
     }
     std::vector<uint32_t> h(n);
     e = hipMemcpyAsync(h.data(), d_flags, (size_t)n * 4, hipMemcpyDeviceToHost, st);
@@ -1204,15 +940,8 @@ int hbec_host_device_addr(const void* p, uint64_t len, uint64_t* dev) {
 int hbec_encode_host(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n_stripes) {
     return hbec::guarded("hbec_encode_host", [&]() -> int {
         if (!codec || (n_stripes && !stripes)) return fail(HBEC_ERR_INVALID_ARG, "null argument");
-        const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
-        if (m == 0) return HBEC_OK;
-        std::vector<uint8_t> mat((size_t)(k + m) * k);
-        hbec_matrix(codec, mat.data());
-        std::vector<uint8_t> rows(mat.begin() + (size_t)k * k, mat.end());
-        std::vector<int> in_idx(k), out_idx(m);
-        for (int j = 0; j < k; ++j) in_idx[j] = j;
-        for (int r = 0; r < m; ++r) out_idx[r] = k + r;
-        return host_run(stripes, n_stripes, in_idx, out_idx, rows);
+        if (hbec_parity_shards(codec) == 0) return HBEC_OK;
+        return encode_host_run(codec, stripes, n_stripes);
     });
 }
 
@@ -1224,12 +953,6 @@ int hbec_encode_host_md5(hbec_codec* codec, const hbec_stripe* stripes, uint64_t
         if (m == 0) return fail(HBEC_ERR_INVALID_ARG, "encode_host_md5 needs parity shards");
         for (uint64_t s = 0; s < n_stripes; ++s)
             if (stripes[s].shard_len == 0) return fail(HBEC_ERR_SHARD_NO_DATA, "stripe with zero shard length");
-        std::vector<uint8_t> mat((size_t)n * k);
-        hbec_matrix(codec, mat.data());
-        std::vector<uint8_t> rows(mat.begin() + (size_t)k * k, mat.end());
-        std::vector<int> in_idx(k), out_idx(m);
-        for (int j = 0; j < k; ++j) in_idx[j] = j;
-        for (int r = 0; r < m; ++r) out_idx[r] = k + r;
         hipStream_t st = nullptr;
         int rc0 = stream_acquire(&st);
         if (rc0) return rc0;
@@ -1245,7 +968,7 @@ int hbec_encode_host_md5(hbec_codec* codec, const hbec_stripe* stripes, uint64_t
             e = hipStreamSynchronize(st);  // allocation visible to the ring's streams
             if (e != hipSuccess) rc = hip_fail(e, "scratch");
         }
-        if (!rc) rc = host_run(stripes, n_stripes, in_idx, out_idx, rows, static_cast<uint8_t*>(d_dig), n);
+        if (!rc) rc = encode_host_run(codec, stripes, n_stripes, static_cast<uint8_t*>(d_dig));
         if (!rc) {
             e = hipMemcpyAsync(digests, d_dig, bytes, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1328,7 +1051,7 @@ int hbec_reconstruct_host(hbec_codec* codec, const hbec_stripe* stripes, uint64_
         if (rc) return rc;
         outs.resize(n_out);
         rows.resize((size_t)n_out * k);
-        return host_run(stripes, n_stripes, surv, outs, rows);
+        return host_run(stripes, n_stripes, Pass{surv, outs, rows});
     });
 }
 
@@ -1343,20 +1066,7 @@ int hbec_verify_host(hbec_codec* codec, const hbec_stripe* stripes, uint64_t n_s
         }
         if (n_stripes) std::memset(flags, 0, n_stripes);
         if (hbec_parity_shards(codec) == 0 || !any) return HBEC_OK;
-        Ring* ring = nullptr;
-        int rc = ring_acquire(&ring);
-        if (rc) return rc;
-        struct Releaser {
-            Ring* r;
-            bool ok = false;
-            ~Releaser() {
-                if (!ok) ring_drain(r);
-                ring_release(r);
-            }
-        } rel{ring};
-        rc = verify_host_run_on(ring, codec, stripes, n_stripes, flags);
-        rel.ok = rc == HBEC_OK;
-        return rc;
+        return with_ring([&](Ring* ring) { return verify_host_run_on(ring, codec, stripes, n_stripes, flags); });
     });
 }
 
