@@ -200,6 +200,9 @@ class StripePlan:
                                           starts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(self._h)))
             self.object_start = starts
             self._n = int(starts[-1])
+            # what glue_files cuts the objects by
+            self._content_lengths = [int(x) for x in lens[:len(files)]]
+            self._chunk_size = int(chunk_size)
             return
         self._n = len(objects) if objects is not None else len(stripes)
         if objects is not None:
@@ -512,6 +515,82 @@ class StripePlan:
             self.enc.handle, self._h, starts.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
             rows.ctypes.data_as(N._U8P), rows.shape[0], row_of.ctypes.data_as(C.POINTER(C.c_uint32)), ptr(filter),
             int(filter_bits) & 0xFFFFFFFF, ptr(expected), ptr(digests), ptr(bad), ptr(where), _stream_ptr(stream)))
+
+    def _patterns(self, present):
+        """The distinct rows of an [n, k+m] present array and each entry's row."""
+        import numpy as np
+
+        p = np.asarray(present) != 0
+        if p.ndim != 2 or p.shape[0] != self._n or p.shape[1] != self.enc.DataShards + self.enc.ParityShards:
+            raise ValueError("present must be [n_stripes, k+m]")
+        if self._n == 0:
+            patterns, pattern_of = p.astype(np.uint8), np.zeros(0, np.uint32)
+        else:
+            patterns, pattern_of = np.unique(p.astype(np.uint8), axis=0, return_inverse=True)
+        return (np.ascontiguousarray(patterns, dtype=np.uint8),
+                np.ascontiguousarray(pattern_of.reshape(-1), dtype=np.uint32))
+
+    def glue_mixed(self, present, dsts, lens, stream=None):
+        """ecGlue for every entry in one call (hbec_glue_plan_mixed): entry i's
+        data shards 0..k-1 back to back, their first lens[i] bytes, written to
+        the device address dsts[i] (any alignment).  ``present`` is [n, k+m] as
+        in reconstruct_mixed: a present data shard is copied, a missing one is
+        what ReconstructData computes from the entry's first k present shards.
+        No shard is written; lens[i] = 0 skips the entry, lens[i] <= k * S_i.
+        Queued on the stream."""
+        import numpy as np
+
+        patterns, pattern_of = self._patterns(present)
+        if len(dsts) != self._n or len(lens) != self._n:
+            raise ValueError("dsts and lens need one element per entry")
+        d = (C.c_void_p * max(1, self._n))(*[int(a) for a in dsts])
+        ln = np.zeros(max(1, self._n), np.uint64)
+        ln[:self._n] = [int(x) for x in lens]
+        check(N.lib().hbec_glue_plan_mixed(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, ln.ctypes.data_as(C.POINTER(C.c_uint64)),
+            _stream_ptr(stream)))
+
+    def glue_files(self, present, outs, stream=None):
+        """glue_mixed for a ``files=`` plan, object by object
+        (hbec_glue_plan_files): object g is written whole, its content length
+        in bytes, at the device address outs[g].  ``present`` stays per ENTRY
+        ([object_start[-1], k+m]): a file may fail between two stripes."""
+        import numpy as np
+
+        if getattr(self, "_content_lengths", None) is None:
+            raise ValueError("glue_files needs a plan built from files=")
+        patterns, pattern_of = self._patterns(present)
+        n_obj = len(self._content_lengths)
+        if len(outs) != n_obj:
+            raise ValueError("outs needs one address per object")
+        d = (C.c_void_p * max(1, n_obj))(*[int(a) for a in outs])
+        ln = np.zeros(max(1, n_obj), np.uint64)
+        ln[:n_obj] = self._content_lengths
+        starts = np.ascontiguousarray(self.object_start, dtype=np.uint32)
+        check(N.lib().hbec_glue_plan_files(
+            self.enc.handle, self._h, starts.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
+            ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), patterns.ctypes.data_as(N._U8P),
+            patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, _stream_ptr(stream)))
+
+
+def glue_plan_stats():
+    """Since load, for StripePlan.glue_mixed / glue_files: launches of the glue
+    kernel (`kernel_launches`) and, on the per-entry route, device-to-device
+    copies and single-pattern applies (`per_stripe_calls`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_glue_plan_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "per_stripe_calls": b.value}
+
+
+def glue_plan_tile_bytes() -> int:
+    """Shard bytes per wave tile of the glue kernel."""
+    return int(N.lib().hbec_glue_plan_tile_bytes())
+
+
+def set_glue_plan_chunk_tiles(tiles: int) -> None:
+    """Test hook: glue kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_glue_plan_chunk_tiles(int(tiles)))
 
 
 def hash_files_stats():

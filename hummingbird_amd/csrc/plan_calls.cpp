@@ -12,7 +12,10 @@
 // stages its chain list where those calls stage their words.  The hash of
 // multi-stripe shard files (hbec_hash_plan_files; hashfiles.h, hashfiles.hip)
 // reads the same records and stages its chains and object table there too.
-// All seven stage and launch through staged_launches; plan.cpp builds the plans.
+// The object bytes of every entry from its shards (hbec_glue_plan_mixed and its
+// object-level form hbec_glue_plan_files; glue.h, glue.hip) walk Reconstruct's
+// records and list and stage a destination per entry beside the words.
+// All of them stage and launch through staged_launches; plan.cpp builds the plans.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +29,7 @@
 
 #include "../../include/hbec.h"
 #include "gf256.h"
+#include "glue.h"
 #include "hashfiles.h"
 #include "hashplan.h"
 #include "heal.h"
@@ -48,7 +52,7 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
     std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal); chains (hash calls)
@@ -800,6 +804,178 @@ int hash_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* ob
     });
 }
 
+// ---- the object bytes of every entry from its shards (hbec_glue_plan_mixed) ----
+
+// The other route (any k, m, S), one source entry: every present data shard with
+// a byte wanted is one device-to-device copy, clipped; the missing ones with a
+// byte wanted are rebuilt by one single-pattern apply, straight into the
+// destination where the shard is written whole, through scratch and a clipped
+// copy where it is cut (at most one shard of an entry is).  Every copy and every
+// apply counts as a per-stripe call.
+int glue_other_entry(const hbec_plan* plan, uint32_t i, const uint8_t* mask, const ShardSet& out, uint64_t dst,
+                     uint64_t len, hipStream_t stream) {
+    const int k = plan->k;
+    const uint64_t S = plan->src[i].shard_len;
+    auto copy = [&](uint64_t to, const void* from, uint64_t bytes) -> int {
+        count(g_calls[kGlue].second);
+        const hipError_t e = hipMemcpyAsync(reinterpret_cast<void*>(to), from, bytes, hipMemcpyDeviceToDevice, stream);
+        return e == hipSuccess ? HBEC_OK : hip_fail(e, "hipMemcpyAsync (glue)");
+    };
+    for (int j = 0; j < k; ++j) {
+        const uint64_t V = hbec::glue_valid(len, (uint64_t)j, S);
+        if (!V || !mask[j]) continue;
+        const int rc = copy(dst + (uint64_t)j * S, reinterpret_cast<const void*>(shard_addr(plan, i, j)), V);
+        if (rc) return rc;
+    }
+    std::vector<size_t> sel;  // the rebuilt shards with a byte wanted, as positions in out.idx
+    size_t cut = out.idx.size();
+    for (size_t q = 0; q < out.idx.size(); ++q) {
+        const uint64_t V = hbec::glue_valid(len, (uint64_t)out.idx[q], S);
+        if (!V) continue;
+        if (V < S) cut = q;
+        sel.push_back(q);
+    }
+    if (sel.empty()) return HBEC_OK;
+    void* scratch = nullptr;
+    if (cut < out.idx.size()) {
+        const int rc = hbec::scratch_alloc((size_t)S, stream, &scratch);
+        if (rc) return rc;
+    }
+    std::vector<hbec_view> vin((size_t)k), vout(sel.size());
+    std::vector<uint8_t> rows(sel.size() * (size_t)k);
+    for (int j = 0; j < k; ++j) vin[j] = hbec_view{reinterpret_cast<void*>(shard_addr(plan, i, out.surv[j])), 0};
+    for (size_t s = 0; s < sel.size(); ++s) {
+        const size_t q = sel[s];
+        vout[s] = hbec_view{q == cut ? scratch : reinterpret_cast<void*>(dst + (uint64_t)out.idx[q] * S), 0};
+        std::memcpy(rows.data() + s * (size_t)k, out.rows.data() + q * (size_t)k, (size_t)k);
+    }
+    count(g_calls[kGlue].second);
+    int rc = hbec::apply_views((int)sel.size(), k, rows.data(), vin.data(), vout.data(), 1, S, stream);
+    if (!rc && scratch)
+        rc = copy(dst + (uint64_t)out.idx[cut] * S, scratch, hbec::glue_valid(len, (uint64_t)out.idx[cut], S));
+    if (scratch) hbec::scratch_free(scratch, stream);
+    return rc;
+}
+
+int glue_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                    const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens, hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    if (!dsts || !dst_lens) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = plan->k, n = k + plan->m;
+    const uint64_t n_src = plan->n_src;
+    bool any = false;
+    for (uint64_t i = 0; i < n_src; ++i) {  // zero-length entries too
+        const uint64_t S = plan->src[i].shard_len, len = dst_lens[i];
+        const uint64_t dst = reinterpret_cast<uintptr_t>(dsts[i]);
+        if ((unsigned __int128)len > (unsigned __int128)S * (uint64_t)k)
+            return fail(HBEC_ERR_INVALID_ARG, "dst_lens exceeds k * shard_len (entry " + std::to_string(i) + ")");
+        if (!len) continue;
+        if (!dst) return fail(HBEC_ERR_INVALID_ARG, "null destination with dst_lens > 0 (entry " + std::to_string(i) + ")");
+        for (int sh = 0; sh < n; ++sh)
+            if (hbec::glue_overlaps(dst, len, shard_addr(plan, (uint32_t)i, sh), S))
+                return fail(HBEC_ERR_INVALID_ARG, "destination overlaps shard " + std::to_string(sh) +
+                                                      " of its own entry (entry " + std::to_string(i) + ")");
+        any = true;
+    }
+    if (!any) return HBEC_OK;  // nothing asked for
+    bool used = false;
+    rc = resolve_patterns(codec, patterns, true, true, false, pats, &used);
+    if (rc) return rc;
+    rc = mixed_plan_device(plan);
+    if (rc) return rc;
+
+    if (plan->n_mtiles > 0) {
+        // Every pattern in use has a record, the masks with no data shard missing
+        // too (r = 0, the header alone: survivors 0..k-1): the tile gathers through
+        // its survivor list.  Then one word per source entry and its destination;
+        // one launch per chunk of the list, of the instance for the largest count
+        // of missing data shards in use.
+        int rmax = -1;
+        std::vector<int> data((size_t)k);
+        for (int j = 0; j < k; ++j) data[j] = j;
+        std::vector<uint32_t> stage;
+        const size_t rec_words = stage_patterns(
+            plan, pats, pattern_of, stage,
+            [&](PlanPattern& pp) {
+                const ShardSet& o = pp.out;
+                pp.rec = o.idx.empty()
+                             ? hbec::mp_pattern(stage, k, data.data(), nullptr, 0, nullptr)
+                             : hbec::mp_pattern(stage, k, o.surv.data(), o.idx.data(), (int)o.idx.size(), o.rows.data());
+            },
+            [&](uint64_t i, const PlanPattern& pp) {
+                const uint64_t S = plan->src[i].shard_len;
+                if (S == 0 || !hbec::pos32_shard(S) || dst_lens[i] == 0) return hbec::kGlueSkip;  // mp_build's route
+                const int r = (int)pp.out.idx.size();
+                rmax = std::max(rmax, r);
+                return ((uint32_t)r << hbec::kMPatShift) | pp.rec;
+            });
+        const size_t dst_at = stage.size();
+        stage.resize(dst_at + 4 * (size_t)n_src);
+        for (uint64_t i = 0; i < n_src; ++i) {
+            const uint64_t dst = reinterpret_cast<uintptr_t>(dsts[i]), len = dst_lens[i];
+            uint32_t* d = stage.data() + dst_at + 4 * i;
+            d[0] = (uint32_t)dst, d[1] = (uint32_t)(dst >> 32), d[2] = (uint32_t)len, d[3] = (uint32_t)(len >> 32);
+        }
+        if (rmax >= 0) {
+            int cus = 0;
+            rc = current_cus(&cus);
+            if (rc) return rc;
+            rc = staged_launches(plan, stage, stream, [&](const uint32_t* d_pats) {
+                return walk_chunks(kGlue, plan->n_mtiles, "launch gf_glue_plan", [&](uint64_t t0, uint32_t nt) {
+                    return (hipError_t)hbec::launch_glue_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt,
+                                                              d_pats + rec_words, d_pats + dst_at, d_pats, cus, stream,
+                                                              plan->shards);
+                });
+            });
+            if (rc) return rc;
+        }
+    }
+    // the other route, one entry at a time (any k, m, S)
+    for (uint32_t i : plan->mp_other) {
+        if (!dst_lens[i]) continue;
+        rc = glue_other_entry(plan, i, patterns + (size_t)pattern_of[i] * n, pats[pattern_of[i]].out,
+                              reinterpret_cast<uintptr_t>(dsts[i]), dst_lens[i], stream);
+        if (rc) return rc;
+    }
+    return HBEC_OK;
+}
+
+// ---- whole objects of a files plan from their shard files (hbec_glue_plan_files) ----
+
+int glue_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                    const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
+                    uint32_t n_patterns, const uint32_t* pattern_of, void* const* object_dsts, hipStream_t stream) {
+    if (!codec || !plan || !content_lengths || !object_dsts) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
+    const uint64_t n_src = plan->n_src;
+    std::vector<void*> dsts((size_t)std::max<uint64_t>(1, n_src), nullptr);
+    std::vector<uint64_t> lens((size_t)std::max<uint64_t>(1, n_src), 0u);
+    if (n_src) {
+        if (const char* why = hbec::files_check_objects(object_start, n_objects, n_src))
+            return fail(HBEC_ERR_INVALID_ARG, why);
+        if (chunk_size == 0 || chunk_size > (uint64_t)INT64_MAX) return fail(HBEC_ERR_INVALID_ARG, "chunk_size out of range");
+        for (uint32_t g = 0; g < n_objects; ++g) {
+            const uint64_t L = content_lengths[g], cnt = object_start[g + 1] - object_start[g];
+            if (L > (uint64_t)INT64_MAX || hbec::ec_stripe_count((int64_t)L, k, (int64_t)chunk_size) != cnt)
+                return fail(HBEC_ERR_INVALID_ARG, "content length does not give the entry count (object " +
+                                                      std::to_string(g) + ")");
+            for (uint64_t t = 0; t < cnt; ++t) {
+                const uint64_t i = object_start[g] + t;
+                if (plan->src[i].shard_len != hbec::ec_stripe_shard_length((int64_t)L, k, (int64_t)chunk_size, t))
+                    return fail(HBEC_ERR_INVALID_ARG, "shard length mismatch (object " + std::to_string(g) +
+                                                          ", stripe " + std::to_string(t) + ")");
+                uint64_t off = 0;
+                hbec::glue_files_cut(L, (uint64_t)k, chunk_size, t, &off, &lens[i]);
+                dsts[i] = object_dsts[g] ? static_cast<uint8_t*>(object_dsts[g]) + off : nullptr;
+            }
+        }
+    }
+    return glue_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), lens.data(), stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -930,6 +1106,33 @@ int hbec_hash_files_stats(uint64_t* kernel_launches, uint64_t* chains, uint64_t*
     const int rc = call_stats("hbec_hash_files_stats", kHashFiles, kernel_launches, segments ? chains : nullptr);
     if (rc == HBEC_OK) *segments = g_hashfiles_segments.load(std::memory_order_relaxed);
     return rc;
+}
+
+int hbec_glue_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                         const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens, void* hip_stream) {
+    return hbec::guarded("hbec_glue_plan_mixed", [&]() -> int {
+        return glue_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, dsts, dst_lens,
+                               static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_glue_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                         const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
+                         uint32_t n_patterns, const uint32_t* pattern_of, void* const* object_dsts, void* hip_stream) {
+    return hbec::guarded("hbec_glue_plan_files", [&]() -> int {
+        return glue_plan_files(codec, plan, object_start, n_objects, content_lengths, chunk_size, patterns, n_patterns,
+                               pattern_of, object_dsts, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_glue_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
+    return call_stats("hbec_glue_plan_stats", kGlue, kernel_launches, per_stripe_calls);
+}
+
+int hbec_glue_plan_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
+
+int hbec_set_glue_plan_chunk_tiles(uint64_t tiles) {
+    return set_chunk_tiles("hbec_set_glue_plan_chunk_tiles", kGlue, tiles);
 }
 
 }  // extern "C"

@@ -676,6 +676,59 @@ typedef struct {
 int hbec_plan_files(hbec_codec* codec, const hbec_file_object* objects, uint32_t n_objects, uint64_t chunk_size,
                     uint32_t* object_start, hbec_plan** out);
 
+/* ecGlue (ecutils.go:134-186) for every entry of a plan in one call: the GET path of a
+ * batch whose shards are in device memory, degraded or not.  Per stripe ecGlue runs
+ * ReconstructData and writes data shards 0..k-1 back to back, cut at the object's
+ * remaining length.  patterns / n_patterns / pattern_of: host arrays exactly as in
+ * hbec_reconstruct_plan_mixed, with the same checks, precedence and messages.  dsts /
+ * dst_lens: host arrays, one element per source entry (zero-length entries included);
+ * dsts holds device addresses at any alignment; both are copied before the call returns.
+ * For entry i let D_i = data shard 0 || ... || data shard k-1 (k * S_i bytes), where a
+ * present data shard contributes its stored bytes and a missing one what ReconstructData
+ * computes from the entry's first k present shards (hbec_decode_rows with data_only = 1).
+ * The call writes D_i[0, dst_lens[i]) to dsts[i] and nothing else: no byte of any shard
+ * (unlike reconstruct, the call is read-only on the plan's buffers) and no byte outside
+ * [dsts[i], dsts[i] + dst_lens[i]).  Only the entry's first k present shards are read
+ * (every present data shard is among them), and no shard position at or past
+ * min(S_i, dst_lens[i]).  dst_lens[i] = 0 skips the entry; a prefix shorter than
+ * k * S_i - (k - 1) is allowed (a ranged GET whose range ends inside the stripe).
+ * Errors, all HBEC_ERR_INVALID_ARG (after hbec_reconstruct_plan_mixed's own) and all
+ * found before anything is queued: a null dsts or dst_lens; dst_lens[i] > k * S_i; a
+ * null dsts[i] with dst_lens[i] > 0; a destination range that overlaps one of the same
+ * entry's k+m shards (ranges that touch do not).  Overlap between different entries'
+ * destinations, or with other entries' shards, is the caller's to answer for.
+ * The work is queued on hip_stream and not waited for.  k <= 12 with m <= 4 runs as one
+ * launch (per 2^31 - 1 tiles) whatever the entries, masks or lengths; a call with
+ * nothing to write launches nothing.  Other shapes, and shards of 2^31 - 64 KiB bytes or
+ * more, go per entry: every present data shard with a byte wanted is one clipped
+ * device-to-device copy, and the missing ones are rebuilt by one single-pattern apply,
+ * straight into the destination where the shard is written whole, through stream-ordered
+ * scratch and a clipped copy where it is cut.  Calls on one plan take turns with the
+ * other _mixed calls, as hbec_reconstruct_plan_mixed's do. */
+int hbec_glue_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                         const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens,
+                         void* hip_stream);
+/* The object-level form for hbec_plan_files plans: object g (entries [object_start[g],
+ * object_start[g+1])) is written whole, content_lengths[g] bytes at object_dsts[g].  Entry t
+ * of the object gets dst = object_dsts[g] + t * k * chunk_size and
+ * len = min(k * S_t, L_g - t * k * chunk_size).  pattern_of stays per ENTRY, as in every
+ * _mixed call: ecGlue's failed[] can change between stripes.  Errors, HBEC_ERR_INVALID_ARG
+ * and found before anything is queued: a null codec, plan, content_lengths or object_dsts;
+ * another (k, m); for a plan with entries, what hbec_hash_plan_files says of object_start,
+ * chunk_size = 0, and a content length whose stripes (hbec_ec_stripe_count,
+ * hbec_ec_stripe_shard_length) are not the object's entries, named by object.  After
+ * these checks it is hbec_glue_plan_mixed. */
+int hbec_glue_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                         const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
+                         uint32_t n_patterns, const uint32_t* pattern_of, void* const* object_dsts,
+                         void* hip_stream);
+/* launches since load of the glue kernel, and copies and applies of the per-entry route */
+int hbec_glue_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
+/* shard bytes per wave tile of the glue kernel */
+int hbec_glue_plan_tile_bytes(void);
+/* test hook, as hbec_set_mixed_plan_chunk_tiles */
+int hbec_set_glue_plan_chunk_tiles(uint64_t tiles);
+
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
  * kernel and D2H of successive chunks overlap on three streams.  Synchronous:
