@@ -160,6 +160,12 @@ _SIG = [
     ("hbec_glue_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_glue_plan_tile_bytes", C.c_int, []),
     ("hbec_set_glue_plan_chunk_tiles", C.c_int, [C.c_uint64]),
+    ("hbec_split_plan", C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64), _P]),
+    ("hbec_split_plan_files", C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64,
+                                        _P, _P]),
+    ("hbec_split_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_split_plan_tile_bytes", C.c_int, []),
+    ("hbec_set_split_plan_chunk_tiles", C.c_int, [C.c_uint64]),
     ("hbec_verify_host", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64, _U8P]),
     ("hbec_encode_host", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64]),
     ("hbec_host_alloc", C.c_int, [C.c_size_t, C.POINTER(_P)]),

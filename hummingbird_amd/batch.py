@@ -573,6 +573,43 @@ class StripePlan:
             ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), patterns.ctypes.data_as(N._U8P),
             patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, _stream_ptr(stream)))
 
+    def split(self, srcs, lens, stream=None):
+        """ecSplit for every entry in one call (hbec_split_plan), the inverse
+        of glue_mixed: the lens[i] bytes at the device address srcs[i] (any
+        alignment) are cut into entry i's k data shards, zero-padded as ecSplit
+        pads its last stripe, and its m parity shards are coded from them.  All
+        k+m shards are written whole; the source is read once.  lens[i] = 0
+        skips the entry; otherwise ceil(lens[i] / k) must be the entry's shard
+        length.  Queued on the stream."""
+        import numpy as np
+
+        if len(srcs) != self._n or len(lens) != self._n:
+            raise ValueError("srcs and lens need one element per entry")
+        d = (C.c_void_p * max(1, self._n))(*[int(a) for a in srcs])
+        ln = np.zeros(max(1, self._n), np.uint64)
+        ln[:self._n] = [int(x) for x in lens]
+        check(N.lib().hbec_split_plan(self.enc.handle, self._h, d, ln.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      _stream_ptr(stream)))
+
+    def split_files(self, srcs, stream=None):
+        """split for a ``files=`` plan, object by object (hbec_split_plan_files):
+        object g, its content length in bytes at the device address srcs[g],
+        is written as its k+m shard files, which is ecSplit for the batch."""
+        import numpy as np
+
+        if getattr(self, "_content_lengths", None) is None:
+            raise ValueError("split_files needs a plan built from files=")
+        n_obj = len(self._content_lengths)
+        if len(srcs) != n_obj:
+            raise ValueError("srcs needs one address per object")
+        d = (C.c_void_p * max(1, n_obj))(*[int(a) for a in srcs])
+        ln = np.zeros(max(1, n_obj), np.uint64)
+        ln[:n_obj] = self._content_lengths
+        starts = np.ascontiguousarray(self.object_start, dtype=np.uint32)
+        check(N.lib().hbec_split_plan_files(
+            self.enc.handle, self._h, starts.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
+            ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), d, _stream_ptr(stream)))
+
 
 def glue_plan_stats():
     """Since load, for StripePlan.glue_mixed / glue_files: launches of the glue
@@ -591,6 +628,25 @@ def glue_plan_tile_bytes() -> int:
 def set_glue_plan_chunk_tiles(tiles: int) -> None:
     """Test hook: glue kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_glue_plan_chunk_tiles(int(tiles)))
+
+
+def split_plan_stats():
+    """Since load, for StripePlan.split / split_files: launches of the split
+    kernel (`kernel_launches`) and, on the per-entry route, device-to-device
+    copies, memsets and applies (`per_stripe_calls`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_split_plan_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "per_stripe_calls": b.value}
+
+
+def split_plan_tile_bytes() -> int:
+    """Shard bytes per wave tile of the split kernel."""
+    return int(N.lib().hbec_split_plan_tile_bytes())
+
+
+def set_split_plan_chunk_tiles(tiles: int) -> None:
+    """Test hook: split kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_split_plan_chunk_tiles(int(tiles)))
 
 
 def hash_files_stats():

@@ -812,6 +812,8 @@ void hbec_plan_free(hbec_plan* plan) {
     if (plan->d_vtab) (void)hipFree(plan->d_vtab);
     if (plan->d_mrecs) (void)hipFree(plan->d_mrecs);
     if (plan->d_mtiles) (void)hipFree(plan->d_mtiles);
+    if (plan->d_sprecs) (void)hipFree(plan->d_sprecs);
+    if (plan->d_sptiles) (void)hipFree(plan->d_sptiles);
     if (plan->d_mstage) (void)hipFree(plan->d_mstage);
     if (plan->d_heal) (void)hipFree(plan->d_heal);
     if (plan->d_hrecs) (void)hipFree(plan->d_hrecs);

@@ -14,7 +14,10 @@
 // reads the same records and stages its chains and object table there too.
 // The object bytes of every entry from its shards (hbec_glue_plan_mixed and its
 // object-level form hbec_glue_plan_files; glue.h, glue.hip) walk Reconstruct's
-// records and list and stage a destination per entry beside the words.
+// records and list and stage a destination per entry beside the words.  The
+// inverse, every entry's shards from its object bytes (hbec_split_plan and
+// hbec_split_plan_files; splitplan.h, splitplan.hip), walks them too and stages
+// a source per entry.
 // All of them stage and launch through staged_launches; plan.cpp builds the plans.
 #include <hip/hip_runtime.h>
 
@@ -40,6 +43,7 @@
 #include "plan_internal.h"
 #include "repair.h"
 #include "shardplan.h"
+#include "splitplan.h"
 #include "vmixed.h"
 
 using hbec::current_cus;
@@ -52,7 +56,7 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
     std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal); chains (hash calls)
@@ -173,26 +177,34 @@ Queued walk_chunks(Call c, uint64_t n_tiles, const char* what, Launch&& launch) 
 
 // ---- the patterns of a call ----
 
-// The device side of a plan's calls with a pattern per entry, built once.
-int mixed_plan_device(const hbec_plan* p) {
+// The device side of the calls that walk a plan's {entry, tile} list, built
+// once: records and list into the plan's fields given, the entries of the other
+// route into *other.  route_m: the parity count the entries are routed by.
+int walk_list_device(const hbec_plan* p, int route_m, bool* built, hbec::MRec** d_recs, hbec::MTile** d_tiles,
+                     uint64_t* n_tiles, std::vector<uint32_t>* other) {
     std::lock_guard<std::mutex> lk(p->mp_mu);
-    if (p->mp_built) return HBEC_OK;
+    if (*built) return HBEC_OK;
     hbec::MixedPlanRecs mr;
-    if (!hbec::mp_build(mr, p->k, p->m, p->src, hbec::mixed_plan_tile_bytes()))
+    if (!hbec::mp_build(mr, p->k, route_m, p->src, hbec::mixed_plan_tile_bytes()))
         return fail(HBEC_ERR_INVALID_ARG, "plan too large (>= 2^31 tiles)");
     if (!mr.tiles.empty()) {
-        int rc = upload(mr.recs, &p->d_mrecs, "plan mixed records");
-        if (!rc) rc = upload(mr.tiles, &p->d_mtiles, "plan mixed tile list");
+        int rc = upload(mr.recs, d_recs, "plan mixed records");
+        if (!rc) rc = upload(mr.tiles, d_tiles, "plan mixed tile list");
         if (rc) {
-            if (p->d_mrecs) (void)hipFree(p->d_mrecs);
-            p->d_mrecs = nullptr;
+            if (*d_recs) (void)hipFree(*d_recs);
+            *d_recs = nullptr;
             return rc;
         }
     }
-    p->n_mtiles = mr.tiles.size();
-    p->mp_other = std::move(mr.other);
-    p->mp_built = true;
+    *n_tiles = mr.tiles.size();
+    *other = std::move(mr.other);
+    *built = true;
     return HBEC_OK;
+}
+
+// The device side of a plan's calls with a pattern per entry.
+int mixed_plan_device(const hbec_plan* p) {
+    return walk_list_device(p, p->m, &p->mp_built, &p->d_mrecs, &p->d_mtiles, &p->n_mtiles, &p->mp_other);
 }
 
 // Shards computed from a pattern's k survivors: idx.size() x k coefficients.
@@ -976,6 +988,156 @@ int glue_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* ob
     return glue_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), lens.data(), stream);
 }
 
+// ---- the k + m shards of every entry from its object bytes (hbec_split_plan) ----
+
+// The other route (any k, m, S), one source entry: every data shard with a byte
+// of the piece is one device-to-device copy, clipped; ecSplit's pad is one
+// memset per data shard it reaches; the parity is one apply of the encode rows
+// over the data shards just written.  Every copy, memset and apply counts as a
+// per-stripe call.
+int split_other_entry(const hbec_plan* plan, uint32_t i, const std::vector<uint8_t>& rows, uint64_t src, uint64_t len,
+                      hipStream_t stream) {
+    const int k = plan->k, m = plan->m;
+    const uint64_t S = plan->src[i].shard_len;
+    for (int j = 0; j < k; ++j) {
+        const uint64_t V = hbec::split_valid(len, (uint64_t)j, S);
+        uint8_t* shard = reinterpret_cast<uint8_t*>(shard_addr(plan, i, j));
+        hipError_t e = hipSuccess;
+        if (V) {
+            count(g_calls[kSplit].second);
+            e = hipMemcpyAsync(shard, reinterpret_cast<const void*>(src + (uint64_t)j * S), V,
+                               hipMemcpyDeviceToDevice, stream);
+            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync (split)");
+        }
+        if (V < S) {
+            count(g_calls[kSplit].second);
+            e = hipMemsetAsync(shard + V, 0, S - V, stream);
+            if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync (split)");
+        }
+    }
+    if (m == 0) return HBEC_OK;
+    std::vector<hbec_view> vin((size_t)k), vout((size_t)m);
+    for (int j = 0; j < k; ++j) vin[j] = hbec_view{reinterpret_cast<void*>(shard_addr(plan, i, j)), 0};
+    for (int r = 0; r < m; ++r) vout[r] = hbec_view{reinterpret_cast<void*>(shard_addr(plan, i, k + r)), 0};
+    count(g_calls[kSplit].second);
+    return hbec::apply_views(m, k, rows.data(), vin.data(), vout.data(), 1, S, stream);
+}
+
+int split_plan(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
+               hipStream_t stream) {
+    if (!codec || !plan || !srcs || !src_lens) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
+    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
+    const uint64_t n_src = plan->n_src;
+    bool any = false;
+    for (uint64_t i = 0; i < n_src; ++i) {  // zero-length entries too
+        const uint64_t S = plan->src[i].shard_len, len = src_lens[i];
+        const uint64_t src = reinterpret_cast<uintptr_t>(srcs[i]);
+        if (!len) continue;
+        if (!hbec::split_len_ok(len, (uint64_t)k, S))
+            return fail(HBEC_ERR_INVALID_ARG,
+                        "src_lens does not give the entry's shard length (entry " + std::to_string(i) + ")");
+        if (!src) return fail(HBEC_ERR_INVALID_ARG, "null source with src_lens > 0 (entry " + std::to_string(i) + ")");
+        for (int sh = 0; sh < n; ++sh)
+            if (hbec::glue_overlaps(src, len, shard_addr(plan, (uint32_t)i, sh), S))
+                return fail(HBEC_ERR_INVALID_ARG, "source overlaps shard " + std::to_string(sh) +
+                                                      " of its own entry (entry " + std::to_string(i) + ")");
+        any = true;
+    }
+    if (!any) return HBEC_OK;  // nothing given
+    // a plan of m = 0 has a list of the call's own (plan_internal.h)
+    const bool own = m == 0;
+    int rc = own ? walk_list_device(plan, 1, &plan->sp_built, &plan->d_sprecs, &plan->d_sptiles, &plan->n_sptiles,
+                                    &plan->sp_other)
+                 : mixed_plan_device(plan);
+    if (rc) return rc;
+    const hbec::MRec* d_recs = own ? plan->d_sprecs : plan->d_mrecs;
+    const hbec::MTile* d_tiles = own ? plan->d_sptiles : plan->d_mtiles;
+    const uint64_t n_tiles = own ? plan->n_sptiles : plan->n_mtiles;
+    const std::vector<uint32_t>& other = own ? plan->sp_other : plan->mp_other;
+    // the encode rows: rows k..k+m-1 of the coding matrix
+    std::vector<uint8_t> mat((size_t)n * k);
+    hbec_matrix(codec, mat.data());
+    const std::vector<uint8_t> rows(mat.begin() + (size_t)k * k, mat.end());
+
+    if (n_tiles > 0) {
+        // One pattern record for the call (data shards in, parity shards out, the
+        // encode rows; for m = 0 the header alone), one word per source entry and
+        // its piece; one launch per chunk of the list, of the instance for m.
+        std::vector<int> data((size_t)k), par((size_t)std::max(1, m));
+        for (int j = 0; j < k; ++j) data[j] = j;
+        for (int r = 0; r < m; ++r) par[r] = k + r;
+        std::vector<uint32_t> stage;
+        const uint32_t rec = hbec::mp_pattern(stage, k, data.data(), m ? par.data() : nullptr, m, m ? rows.data() : nullptr);
+        const size_t rec_words = stage.size();
+        stage.resize(rec_words + 5 * (size_t)n_src);
+        const size_t src_at = rec_words + (size_t)n_src;
+        bool work = false;
+        for (uint64_t i = 0; i < n_src; ++i) {
+            const uint64_t S = plan->src[i].shard_len, len = src_lens[i];
+            const uint64_t src = reinterpret_cast<uintptr_t>(srcs[i]);
+            const bool mine = S != 0 && hbec::pos32_shard(S) && len != 0;  // mp_build's route
+            stage[rec_words + i] = mine ? (((uint32_t)m << hbec::kMPatShift) | rec) : hbec::kSplitSkip;
+            work = work || mine;
+            uint32_t* d = stage.data() + src_at + 4 * i;
+            d[0] = (uint32_t)src, d[1] = (uint32_t)(src >> 32), d[2] = (uint32_t)len, d[3] = (uint32_t)(len >> 32);
+        }
+        if (work) {
+            int cus = 0;
+            rc = current_cus(&cus);
+            if (rc) return rc;
+            rc = staged_launches(plan, stage, stream, [&](const uint32_t* d_pats) {
+                return walk_chunks(kSplit, n_tiles, "launch gf_split_plan", [&](uint64_t t0, uint32_t nt) {
+                    return (hipError_t)hbec::launch_split_plan(k, m, d_recs, d_tiles + t0, nt, d_pats + rec_words,
+                                                               d_pats + src_at, d_pats, cus, stream, plan->shards);
+                });
+            });
+            if (rc) return rc;
+        }
+    }
+    // the other route, one entry at a time (any k, m, S)
+    for (uint32_t i : other) {
+        if (!src_lens[i]) continue;
+        rc = split_other_entry(plan, i, rows, reinterpret_cast<uintptr_t>(srcs[i]), src_lens[i], stream);
+        if (rc) return rc;
+    }
+    return HBEC_OK;
+}
+
+// ---- whole objects of a files plan into their shard files (hbec_split_plan_files) ----
+
+int split_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                     const uint64_t* content_lengths, uint64_t chunk_size, const void* const* object_srcs,
+                     hipStream_t stream) {
+    if (!codec || !plan || !content_lengths || !object_srcs) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
+    const uint64_t n_src = plan->n_src;
+    std::vector<const void*> srcs((size_t)std::max<uint64_t>(1, n_src), nullptr);
+    std::vector<uint64_t> lens((size_t)std::max<uint64_t>(1, n_src), 0u);
+    if (n_src) {
+        if (const char* why = hbec::files_check_objects(object_start, n_objects, n_src))
+            return fail(HBEC_ERR_INVALID_ARG, why);
+        if (chunk_size == 0 || chunk_size > (uint64_t)INT64_MAX) return fail(HBEC_ERR_INVALID_ARG, "chunk_size out of range");
+        for (uint32_t g = 0; g < n_objects; ++g) {
+            const uint64_t L = content_lengths[g], cnt = object_start[g + 1] - object_start[g];
+            if (L > (uint64_t)INT64_MAX || hbec::ec_stripe_count((int64_t)L, k, (int64_t)chunk_size) != cnt)
+                return fail(HBEC_ERR_INVALID_ARG, "content length does not give the entry count (object " +
+                                                      std::to_string(g) + ")");
+            for (uint64_t t = 0; t < cnt; ++t) {
+                const uint64_t i = object_start[g] + t;
+                if (plan->src[i].shard_len != hbec::ec_stripe_shard_length((int64_t)L, k, (int64_t)chunk_size, t))
+                    return fail(HBEC_ERR_INVALID_ARG, "shard length mismatch (object " + std::to_string(g) +
+                                                          ", stripe " + std::to_string(t) + ")");
+                uint64_t off = 0;
+                hbec::glue_files_cut(L, (uint64_t)k, chunk_size, t, &off, &lens[i]);
+                srcs[i] = object_srcs[g] ? static_cast<const uint8_t*>(object_srcs[g]) + off : nullptr;
+            }
+        }
+    }
+    return split_plan(codec, plan, srcs.data(), lens.data(), stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1133,6 +1295,32 @@ int hbec_glue_plan_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
 
 int hbec_set_glue_plan_chunk_tiles(uint64_t tiles) {
     return set_chunk_tiles("hbec_set_glue_plan_chunk_tiles", kGlue, tiles);
+}
+
+int hbec_split_plan(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
+                    void* hip_stream) {
+    return hbec::guarded("hbec_split_plan", [&]() -> int {
+        return split_plan(codec, plan, srcs, src_lens, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_split_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                          const uint64_t* content_lengths, uint64_t chunk_size, const void* const* object_srcs,
+                          void* hip_stream) {
+    return hbec::guarded("hbec_split_plan_files", [&]() -> int {
+        return split_plan_files(codec, plan, object_start, n_objects, content_lengths, chunk_size, object_srcs,
+                                static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_split_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
+    return call_stats("hbec_split_plan_stats", kSplit, kernel_launches, per_stripe_calls);
+}
+
+int hbec_split_plan_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
+
+int hbec_set_split_plan_chunk_tiles(uint64_t tiles) {
+    return set_chunk_tiles("hbec_set_split_plan_chunk_tiles", kSplit, tiles);
 }
 
 }  // extern "C"

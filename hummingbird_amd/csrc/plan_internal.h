@@ -73,6 +73,15 @@ struct hbec_plan {
     mutable size_t mstage_words = 0;
     mutable hipEvent_t mp_ev = nullptr;  // after the last call's launches, on mp_stream
     mutable hipStream_t mp_stream = nullptr;
+    // hbec_split_plan on a plan of m = 0, a scatter: no _mixed call has work
+    // there, so mp_build lists no tile of it and the first split builds records
+    // and a list of its own (mp_mu), routed by k and S alone.  With m > 0 the
+    // call walks d_mrecs / d_mtiles.
+    mutable bool sp_built = false;
+    mutable hbec::MRec* d_sprecs = nullptr;
+    mutable hbec::MTile* d_sptiles = nullptr;
+    mutable uint64_t n_sptiles = 0;
+    mutable std::vector<uint32_t> sp_other;
     // hbec_heal_plan_mixed: the records and tables of the last call's masks, on
     // the host (heal_mu) and on the device (d_heal, under mp_mu and ordered by
     // mp_ev like d_mstage).  They depend on (k, m) and the masks alone, and a

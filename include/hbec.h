@@ -729,6 +729,54 @@ int hbec_glue_plan_tile_bytes(void);
 /* test hook, as hbec_set_mixed_plan_chunk_tiles */
 int hbec_set_glue_plan_chunk_tiles(uint64_t tiles);
 
+/* ecSplit (ecutils.go:26-72) for every entry of a plan in one call: the stabilize path of
+ * a batch whose objects are in device memory, and the inverse of hbec_glue_plan_mixed.
+ * Per stripe ecSplit reads k * S bytes of the object, zero-pads the last stripe to a
+ * multiple of k (:51-54), cuts it into k data shards and encodes m parity shards.  srcs /
+ * src_lens: host arrays, one element per source entry (zero-length entries included);
+ * srcs holds device addresses at any alignment; both are copied before the call returns.
+ * For entry i of any kind of plan let O_i = [srcs[i], srcs[i] + src_lens[i]) and S_i its
+ * shard length.  Data shard j gets O_i[j * S_i + p] at position p where j * S_i + p <
+ * src_lens[i], and 0 otherwise (with a short piece whole trailing data shards are zero);
+ * parity shard r gets row k + r of the coding matrix applied to those data shards.  All
+ * k+m shards of the entry are written whole, [0, S_i) each, and nothing else; the source is
+ * read once and not modified, and no 16-byte block without a byte of O_i is read.
+ * src_lens[i] = 0 skips the entry.  The call takes no mask: a writers mask (ecSplit's nil
+ * writers) is not offered.
+ * Errors, all HBEC_ERR_INVALID_ARG and all found before anything is queued, in this order:
+ * a null codec, plan, srcs or src_lens; a plan built for another (k, m); then per entry
+ * with src_lens[i] > 0, named by entry: a length whose ecShardLength, ceil(src_lens[i] / k),
+ * is not S_i (k * S_i - k < src_lens[i] <= k * S_i); a null srcs[i]; a source range that
+ * overlaps one of the same entry's k+m shards (ranges that touch do not; a caller whose
+ * data shards are in place already uses hbec_encode_plan).
+ * The work is queued on hip_stream and not waited for.  k <= 12 with m <= 4, m = 0
+ * included as a pure scatter, runs as one launch (per 2^31 - 1 tiles) whatever the
+ * entries or lengths; a call with nothing given launches nothing.  Other shapes, and
+ * shards of 2^31 - 64 KiB bytes or more, go per entry: a clipped device-to-device copy per
+ * data shard with a byte of the piece, a memset per data shard the pad reaches, and one
+ * apply for the parity.  Calls on one plan take turns with the _mixed calls. */
+int hbec_split_plan(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
+                    void* hip_stream);
+/* ecSplit itself (ecutils.go:26-72) for a batch, on hbec_plan_files plans: object g
+ * (entries [object_start[g], object_start[g+1])) is read whole, content_lengths[g] bytes at
+ * object_srcs[g], and its k+m shard files are written.  Entry t of the object gets
+ * src = object_srcs[g] + t * k * chunk_size and len = min(k * S_t, L_g - t * k * chunk_size).
+ * Errors, HBEC_ERR_INVALID_ARG and found before anything is queued: a null codec, plan,
+ * content_lengths or object_srcs; another (k, m); for a plan with entries, what
+ * hbec_glue_plan_files says of object_start, chunk_size and the content lengths.  After
+ * these checks it is hbec_split_plan (a null object_srcs[g] of an object with bytes is its
+ * null source). */
+int hbec_split_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                          uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                          const void* const* object_srcs, void* hip_stream);
+/* ecSplit (ecutils.go:26-72) batch call: launches since load of the split kernel, and
+ * copies, memsets and applies of the per-entry route */
+int hbec_split_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
+/* shard bytes per wave tile of the split kernel (ecutils.go:26-72 batch call) */
+int hbec_split_plan_tile_bytes(void);
+/* test hook of the ecutils.go:26-72 batch call, as hbec_set_mixed_plan_chunk_tiles */
+int hbec_set_split_plan_chunk_tiles(uint64_t tiles);
+
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
  * kernel and D2H of successive chunks overlap on three streams.  Synchronous:
