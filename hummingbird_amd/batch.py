@@ -573,6 +573,53 @@ class StripePlan:
             ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), patterns.ctypes.data_as(N._U8P),
             patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, _stream_ptr(stream)))
 
+    def glue_range(self, present, dsts, starts, lens, stream=None):
+        """Any byte range of every entry in one call (hbec_glue_plan_range): with
+        D_i entry i's data shards 0..k-1 back to back as in glue_mixed, the
+        bytes D_i[starts[i], starts[i] + lens[i]) are written to the device
+        address dsts[i] (any alignment), and nothing else.  Tiles of shard
+        positions outside the range are not read, and a part of the range that
+        touches no missing data shard is copied without decoding.  lens[i] = 0
+        skips the entry; starts[i] + lens[i] <= k * S_i.  Queued on the stream."""
+        import numpy as np
+
+        patterns, pattern_of = self._patterns(present)
+        if len(dsts) != self._n or len(starts) != self._n or len(lens) != self._n:
+            raise ValueError("dsts, starts and lens need one element per entry")
+        d = (C.c_void_p * max(1, self._n))(*[int(a) for a in dsts])
+        st, ln = np.zeros(max(1, self._n), np.uint64), np.zeros(max(1, self._n), np.uint64)
+        st[:self._n] = [int(x) for x in starts]
+        ln[:self._n] = [int(x) for x in lens]
+        check(N.lib().hbec_glue_plan_range(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, st.ctypes.data_as(C.POINTER(C.c_uint64)),
+            ln.ctypes.data_as(C.POINTER(C.c_uint64)), _stream_ptr(stream)))
+
+    def glue_range_files(self, present, outs, starts, ends, stream=None):
+        """glue_range for a ``files=`` plan, object by object
+        (hbec_glue_plan_files_range): object g's bytes [starts[g], ends[g]), in
+        object bytes, are written to the device address outs[g].  ``present``
+        stays per ENTRY, as in glue_files."""
+        import numpy as np
+
+        if getattr(self, "_content_lengths", None) is None:
+            raise ValueError("glue_range_files needs a plan built from files=")
+        patterns, pattern_of = self._patterns(present)
+        n_obj = len(self._content_lengths)
+        if len(outs) != n_obj or len(starts) != n_obj or len(ends) != n_obj:
+            raise ValueError("outs, starts and ends need one element per object")
+        d = (C.c_void_p * max(1, n_obj))(*[int(a) for a in outs])
+        ln, st, en = (np.zeros(max(1, n_obj), np.uint64) for _ in range(3))
+        ln[:n_obj] = self._content_lengths
+        st[:n_obj] = [int(x) for x in starts]
+        en[:n_obj] = [int(x) for x in ends]
+        object_start = np.ascontiguousarray(self.object_start, dtype=np.uint32)
+        check(N.lib().hbec_glue_plan_files_range(
+            self.enc.handle, self._h, object_start.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
+            ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), patterns.ctypes.data_as(N._U8P),
+            patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d,
+            st.ctypes.data_as(C.POINTER(C.c_uint64)), en.ctypes.data_as(C.POINTER(C.c_uint64)), _stream_ptr(stream)))
+
     def split(self, srcs, lens, stream=None):
         """ecSplit for every entry in one call (hbec_split_plan), the inverse
         of glue_mixed: the lens[i] bytes at the device address srcs[i] (any
@@ -628,6 +675,25 @@ def glue_plan_tile_bytes() -> int:
 def set_glue_plan_chunk_tiles(tiles: int) -> None:
     """Test hook: glue kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_glue_plan_chunk_tiles(int(tiles)))
+
+
+def glue_range_stats():
+    """Since load, for StripePlan.glue_range / glue_range_files: launches of the
+    range kernel (`kernel_launches`) and, on the per-entry route,
+    device-to-device copies and single-pattern applies (`per_stripe_calls`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_glue_range_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "per_stripe_calls": b.value}
+
+
+def glue_range_tile_bytes() -> int:
+    """Shard bytes per wave tile of the range kernel."""
+    return int(N.lib().hbec_glue_range_tile_bytes())
+
+
+def set_glue_range_chunk_tiles(tiles: int) -> None:
+    """Test hook: range kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_glue_range_chunk_tiles(int(tiles)))
 
 
 def split_plan_stats():

@@ -17,7 +17,9 @@
 // records and list and stage a destination per entry beside the words.  The
 // inverse, every entry's shards from its object bytes (hbec_split_plan and
 // hbec_split_plan_files; splitplan.h, splitplan.hip), walks them too and stages
-// a source per entry.
+// a source per entry.  Any byte range of every entry (hbec_glue_plan_range and
+// hbec_glue_plan_files_range; gluerange.h, gluerange.hip) is the glue call with a
+// start beside each length.
 // All of them stage and launch through staged_launches; plan.cpp builds the plans.
 #include <hip/hip_runtime.h>
 
@@ -33,6 +35,7 @@
 #include "../../include/hbec.h"
 #include "gf256.h"
 #include "glue.h"
+#include "gluerange.h"
 #include "hashfiles.h"
 #include "hashplan.h"
 #include "heal.h"
@@ -56,7 +59,7 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
     std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal); chains (hash calls)
@@ -988,6 +991,198 @@ int glue_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* ob
     return glue_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), lens.data(), stream);
 }
 
+// ---- any byte range of every entry from its shards (hbec_glue_plan_range) ----
+
+// The other route (any k, m, S), one source entry: every present data shard with
+// a byte wanted is one device-to-device copy of its window.  The missing ones
+// with a byte wanted are rebuilt by one single-pattern apply over the shard
+// positions [A, B) their windows span (GF apply is bytewise): straight into the
+// destination where a shard's window is all of [A, B), through scratch and a
+// clipped copy where it is not.  Every copy and every apply counts as a
+// per-stripe call.
+int glue_range_other_entry(const hbec_plan* plan, uint32_t i, const uint8_t* mask, const ShardSet& out, uint64_t dst,
+                           uint64_t s, uint64_t len, hipStream_t stream) {
+    const int k = plan->k;
+    const uint64_t S = plan->src[i].shard_len, e = s + len;
+    auto copy = [&](uint64_t to, uint64_t from, uint64_t bytes) -> int {
+        count(g_calls[kGlueRange].second);
+        const hipError_t err = hipMemcpyAsync(reinterpret_cast<void*>(to), reinterpret_cast<const void*>(from), bytes,
+                                              hipMemcpyDeviceToDevice, stream);
+        return err == hipSuccess ? HBEC_OK : hip_fail(err, "hipMemcpyAsync (glue range)");
+    };
+    for (int j = 0; j < k; ++j) {
+        const hbec::GrWin w = hbec::gr_window(S, s, e, (uint64_t)j);
+        if (hbec::gr_empty(w) || !mask[j]) continue;
+        const int rc = copy(hbec::gr_base(dst, S, s, (uint64_t)j) + w.lo, shard_addr(plan, i, j) + w.lo, w.hi - w.lo);
+        if (rc) return rc;
+    }
+    std::vector<size_t> sel;  // the rebuilt shards with a byte wanted, as positions in out.idx
+    uint64_t A = S, B = 0;
+    for (size_t q = 0; q < out.idx.size(); ++q) {
+        const hbec::GrWin w = hbec::gr_window(S, s, e, (uint64_t)out.idx[q]);
+        if (hbec::gr_empty(w)) continue;
+        A = std::min(A, w.lo), B = std::max(B, w.hi);
+        sel.push_back(q);
+    }
+    if (sel.empty()) return HBEC_OK;
+    auto whole = [&](size_t q) {
+        const hbec::GrWin w = hbec::gr_window(S, s, e, (uint64_t)out.idx[q]);
+        return w.lo == A && w.hi == B;
+    };
+    size_t n_cut = 0;
+    for (size_t q : sel) n_cut += whole(q) ? 0 : 1;
+    void* scratch = nullptr;
+    if (n_cut) {
+        const int rc = hbec::scratch_alloc((size_t)(n_cut * (B - A)), stream, &scratch);
+        if (rc) return rc;
+    }
+    std::vector<hbec_view> vin((size_t)k), vout(sel.size());
+    std::vector<uint8_t> rows(sel.size() * (size_t)k);
+    for (int j = 0; j < k; ++j) vin[j] = hbec_view{reinterpret_cast<void*>(shard_addr(plan, i, out.surv[j]) + A), 0};
+    size_t cut = 0;
+    for (size_t t = 0; t < sel.size(); ++t) {
+        const size_t q = sel[t];
+        const uint64_t at = whole(q) ? hbec::gr_base(dst, S, s, (uint64_t)out.idx[q]) + A
+                                     : reinterpret_cast<uintptr_t>(scratch) + (cut++) * (B - A);
+        vout[t] = hbec_view{reinterpret_cast<void*>(at), 0};
+        std::memcpy(rows.data() + t * (size_t)k, out.rows.data() + q * (size_t)k, (size_t)k);
+    }
+    count(g_calls[kGlueRange].second);
+    int rc = hbec::apply_views((int)sel.size(), k, rows.data(), vin.data(), vout.data(), 1, B - A, stream);
+    for (size_t t = 0; t < sel.size() && !rc; ++t) {
+        if (whole(sel[t])) continue;
+        const hbec::GrWin w = hbec::gr_window(S, s, e, (uint64_t)out.idx[sel[t]]);
+        rc = copy(hbec::gr_base(dst, S, s, (uint64_t)out.idx[sel[t]]) + w.lo,
+                  reinterpret_cast<uintptr_t>(vout[t].base) + (w.lo - A), w.hi - w.lo);
+    }
+    if (scratch) hbec::scratch_free(scratch, stream);
+    return rc;
+}
+
+int glue_plan_range(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                    const uint32_t* pattern_of, void* const* dsts, const uint64_t* starts, const uint64_t* lens,
+                    hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    if (!dsts || !starts || !lens) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = plan->k, n = k + plan->m;
+    const uint64_t n_src = plan->n_src;
+    bool any = false;
+    for (uint64_t i = 0; i < n_src; ++i) {  // zero-length entries too
+        const uint64_t S = plan->src[i].shard_len, len = lens[i];
+        if (!len) continue;  // whatever starts[i] and dsts[i] are
+        const uint64_t dst = reinterpret_cast<uintptr_t>(dsts[i]);
+        if (!hbec::gr_range_ok(starts[i], len, (uint64_t)k, S))
+            return fail(HBEC_ERR_INVALID_ARG, "starts + lens exceeds k * shard_len (entry " + std::to_string(i) + ")");
+        if (!dst) return fail(HBEC_ERR_INVALID_ARG, "null destination with lens > 0 (entry " + std::to_string(i) + ")");
+        for (int sh = 0; sh < n; ++sh)
+            if (hbec::glue_overlaps(dst, len, shard_addr(plan, (uint32_t)i, sh), S))
+                return fail(HBEC_ERR_INVALID_ARG, "destination overlaps shard " + std::to_string(sh) +
+                                                      " of its own entry (entry " + std::to_string(i) + ")");
+        any = true;
+    }
+    if (!any) return HBEC_OK;  // nothing asked for
+    bool used = false;
+    rc = resolve_patterns(codec, patterns, true, true, false, pats, &used);
+    if (rc) return rc;
+    rc = mixed_plan_device(plan);
+    if (rc) return rc;
+
+    if (plan->n_mtiles > 0) {
+        // glue_plan_mixed's staging, with {address, start, length} per source entry
+        int rmax = -1;
+        std::vector<int> data((size_t)k);
+        for (int j = 0; j < k; ++j) data[j] = j;
+        std::vector<uint32_t> stage;
+        const size_t rec_words = stage_patterns(
+            plan, pats, pattern_of, stage,
+            [&](PlanPattern& pp) {
+                const ShardSet& o = pp.out;
+                pp.rec = o.idx.empty()
+                             ? hbec::mp_pattern(stage, k, data.data(), nullptr, 0, nullptr)
+                             : hbec::mp_pattern(stage, k, o.surv.data(), o.idx.data(), (int)o.idx.size(), o.rows.data());
+            },
+            [&](uint64_t i, const PlanPattern& pp) {
+                const uint64_t S = plan->src[i].shard_len;
+                if (S == 0 || !hbec::pos32_shard(S) || lens[i] == 0) return hbec::kGlueSkip;  // mp_build's route
+                const int r = (int)pp.out.idx.size();
+                rmax = std::max(rmax, r);
+                return ((uint32_t)r << hbec::kMPatShift) | pp.rec;
+            });
+        const size_t range_at = stage.size();
+        stage.resize(range_at + 6 * (size_t)n_src);
+        for (uint64_t i = 0; i < n_src; ++i) {
+            const uint64_t v[3] = {reinterpret_cast<uintptr_t>(dsts[i]), starts[i], lens[i]};
+            uint32_t* d = stage.data() + range_at + 6 * i;
+            for (int q = 0; q < 3; ++q) d[2 * q] = (uint32_t)v[q], d[2 * q + 1] = (uint32_t)(v[q] >> 32);
+        }
+        if (rmax >= 0) {
+            int cus = 0;
+            rc = current_cus(&cus);
+            if (rc) return rc;
+            rc = staged_launches(plan, stage, stream, [&](const uint32_t* d_pats) {
+                return walk_chunks(kGlueRange, plan->n_mtiles, "launch gf_range_plan", [&](uint64_t t0, uint32_t nt) {
+                    return (hipError_t)hbec::launch_glue_range(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt,
+                                                               d_pats + rec_words, d_pats + range_at, d_pats, cus,
+                                                               stream, plan->shards);
+                });
+            });
+            if (rc) return rc;
+        }
+    }
+    // the other route, one entry at a time (any k, m, S)
+    for (uint32_t i : plan->mp_other) {
+        if (!lens[i]) continue;
+        rc = glue_range_other_entry(plan, i, patterns + (size_t)pattern_of[i] * n, pats[pattern_of[i]].out,
+                                    reinterpret_cast<uintptr_t>(dsts[i]), starts[i], lens[i], stream);
+        if (rc) return rc;
+    }
+    return HBEC_OK;
+}
+
+// ---- a byte range of whole objects of a files plan (hbec_glue_plan_files_range) ----
+
+int glue_plan_files_range(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                          const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
+                          uint32_t n_patterns, const uint32_t* pattern_of, void* const* object_dsts,
+                          const uint64_t* range_starts, const uint64_t* range_ends, hipStream_t stream) {
+    if (!codec || !plan || !content_lengths || !object_dsts || !range_starts || !range_ends)
+        return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
+    const uint64_t n_src = plan->n_src;
+    std::vector<void*> dsts((size_t)std::max<uint64_t>(1, n_src), nullptr);
+    std::vector<uint64_t> starts((size_t)std::max<uint64_t>(1, n_src), 0u), lens(starts);
+    if (n_src) {
+        if (const char* why = hbec::files_check_objects(object_start, n_objects, n_src))
+            return fail(HBEC_ERR_INVALID_ARG, why);
+        if (chunk_size == 0 || chunk_size > (uint64_t)INT64_MAX) return fail(HBEC_ERR_INVALID_ARG, "chunk_size out of range");
+        for (uint32_t g = 0; g < n_objects; ++g) {
+            const uint64_t L = content_lengths[g], cnt = object_start[g + 1] - object_start[g];
+            if (L > (uint64_t)INT64_MAX || hbec::ec_stripe_count((int64_t)L, k, (int64_t)chunk_size) != cnt)
+                return fail(HBEC_ERR_INVALID_ARG, "content length does not give the entry count (object " +
+                                                      std::to_string(g) + ")");
+            for (uint64_t t = 0; t < cnt; ++t)
+                if (plan->src[object_start[g] + t].shard_len !=
+                    hbec::ec_stripe_shard_length((int64_t)L, k, (int64_t)chunk_size, t))
+                    return fail(HBEC_ERR_INVALID_ARG, "shard length mismatch (object " + std::to_string(g) +
+                                                          ", stripe " + std::to_string(t) + ")");
+            if (range_starts[g] > range_ends[g] || range_ends[g] > L)
+                return fail(HBEC_ERR_INVALID_ARG, "range is not inside the object (object " + std::to_string(g) + ")");
+            for (uint64_t t = 0; t < cnt; ++t) {
+                const uint64_t i = object_start[g] + t;
+                uint64_t off = 0, len = 0, dst_off = 0;
+                hbec::glue_files_cut(L, (uint64_t)k, chunk_size, t, &off, &len);
+                hbec::gr_files_cut(off, len, range_starts[g], range_ends[g], &starts[i], &lens[i], &dst_off);
+                dsts[i] = object_dsts[g] ? static_cast<uint8_t*>(object_dsts[g]) + dst_off : nullptr;
+            }
+        }
+    }
+    return glue_plan_range(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), starts.data(), lens.data(),
+                           stream);
+}
+
 // ---- the k + m shards of every entry from its object bytes (hbec_split_plan) ----
 
 // The other route (any k, m, S), one source entry: every data shard with a byte
@@ -1295,6 +1490,37 @@ int hbec_glue_plan_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
 
 int hbec_set_glue_plan_chunk_tiles(uint64_t tiles) {
     return set_chunk_tiles("hbec_set_glue_plan_chunk_tiles", kGlue, tiles);
+}
+
+int hbec_glue_plan_range(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                         const uint32_t* pattern_of, void* const* dsts, const uint64_t* starts, const uint64_t* lens,
+                         void* hip_stream) {
+    return hbec::guarded("hbec_glue_plan_range", [&]() -> int {
+        return glue_plan_range(codec, plan, patterns, n_patterns, pattern_of, dsts, starts, lens,
+                               static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_glue_plan_files_range(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                               uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                               const uint8_t* patterns, uint32_t n_patterns, const uint32_t* pattern_of,
+                               void* const* object_dsts, const uint64_t* range_starts, const uint64_t* range_ends,
+                               void* hip_stream) {
+    return hbec::guarded("hbec_glue_plan_files_range", [&]() -> int {
+        return glue_plan_files_range(codec, plan, object_start, n_objects, content_lengths, chunk_size, patterns,
+                                     n_patterns, pattern_of, object_dsts, range_starts, range_ends,
+                                     static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_glue_range_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
+    return call_stats("hbec_glue_range_stats", kGlueRange, kernel_launches, per_stripe_calls);
+}
+
+int hbec_glue_range_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
+
+int hbec_set_glue_range_chunk_tiles(uint64_t tiles) {
+    return set_chunk_tiles("hbec_set_glue_range_chunk_tiles", kGlueRange, tiles);
 }
 
 int hbec_split_plan(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,

@@ -729,6 +729,67 @@ int hbec_glue_plan_tile_bytes(void);
 /* test hook, as hbec_set_mixed_plan_chunk_tiles */
 int hbec_set_glue_plan_chunk_tiles(uint64_t tiles);
 
+/* Any byte range of every entry of a plan in one call: the decode of a ranged GET
+ * (ecObject.CopyRange, ecobj.go:207-267) over ecGlue's layout (ecutils.go:134-186) for a
+ * batch whose shards are in device memory, degraded or not.  patterns / n_patterns /
+ * pattern_of: exactly as in hbec_glue_plan_mixed.  dsts / starts / lens: host arrays, one
+ * element per source entry (zero-length entries included), copied before the call returns;
+ * dsts holds device addresses at any alignment.  With D_i as hbec_glue_plan_mixed defines
+ * it, s = starts[i] and e = s + lens[i], the call writes D_i[s, e) to
+ * [dsts[i], dsts[i] + lens[i]) and stores nothing else: no shard byte and no byte outside
+ * that destination range.  lens[i] = 0 skips the entry, whatever starts[i] and dsts[i]
+ * are.  With every start 0 the bytes written are hbec_glue_plan_mixed's.  Data shard j
+ * contributes its positions [lo_j, hi_j), lo_j = clamp(s - j S, 0, S) and
+ * hi_j = clamp(e - j S, 0, S); position p of it lands at dsts[i] + (j S + p - s).
+ * What is read: only the entry's first k present shards, and of them no byte outside
+ * [shard, shard + S) (16-byte blocks are loaded whole where they hold such a byte).  A
+ * tile of shard positions none of which is wanted in any data shard loads nothing: the
+ * wanted positions are one interval when the range lies in one shard, [0, e - j1 S) and
+ * [s - j0 S, S) when it crosses one junction and the two parts do not meet, and [0, S)
+ * otherwise.  A tile in which no MISSING data shard has a wanted position is gathered: it
+ * reads only the present data shards whose window meets it, no parity, and multiplies
+ * nothing, also in an entry whose mask has data shards missing.  Every other live tile
+ * reads the k survivors at its positions and stores only the decoded rows, and the
+ * present data shards, that have a wanted position there.
+ * Errors: hbec_reconstruct_plan_mixed's first; then, all HBEC_ERR_INVALID_ARG, all found
+ * before anything is queued and named by entry: a null dsts, starts or lens;
+ * starts[i] + lens[i] > k * S_i (computed without overflow); a null dsts[i] with
+ * lens[i] > 0; a destination range that overlaps one of the same entry's k+m shards
+ * (ranges that touch do not).
+ * The work is queued on hip_stream and not waited for.  k <= 12 with m <= 4 runs as one
+ * launch (per 2^31 - 1 tiles) whatever the entries, masks or ranges; a call with nothing
+ * to write launches nothing.  Other shapes, and shards of 2^31 - 64 KiB bytes or more, go
+ * per entry: every present data shard with a byte wanted is one clipped device-to-device
+ * copy; the missing ones with a byte wanted are rebuilt by one single-pattern apply over
+ * the shard positions [A, B) their windows span, straight into the destination where a
+ * shard's window is all of [A, B), through stream-ordered scratch and a clipped copy where
+ * it is not.  Calls on one plan take turns with the other _mixed calls. */
+int hbec_glue_plan_range(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                         const uint32_t* pattern_of, void* const* dsts, const uint64_t* starts,
+                         const uint64_t* lens, void* hip_stream);
+/* The object-level form for hbec_plan_files plans (ecobj.go:207-267 over ecutils.go:134-186):
+ * object g's bytes [range_starts[g], range_ends[g]) are written to object_dsts[g].  The
+ * units are OBJECT bytes: this is the corrected decode of hbec_ec_glue_range, not
+ * CopyRange's mixed units (hbec_ec_copy_range stays the byte-exact drop-in for those).
+ * Entry t of the object covers object bytes [off_t, off_t + len_t) as in
+ * hbec_glue_plan_files; it gets the intersection with the range, relative to off_t, at
+ * object_dsts[g] + (max(start, off_t) - start), and length 0 where they do not meet.
+ * pattern_of stays per ENTRY.  Errors: hbec_glue_plan_files's, a null range_starts or
+ * range_ends with its null arguments, and (HBEC_ERR_INVALID_ARG, named by object, checked
+ * after the object's content length) a range that is not 0 <= start <= end <= content
+ * length.  After these checks it is hbec_glue_plan_range. */
+int hbec_glue_plan_files_range(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                               uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                               const uint8_t* patterns, uint32_t n_patterns, const uint32_t* pattern_of,
+                               void* const* object_dsts, const uint64_t* range_starts, const uint64_t* range_ends,
+                               void* hip_stream);
+/* launches since load of the range kernel, and copies and applies of the per-entry route */
+int hbec_glue_range_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
+/* shard bytes per wave tile of the range kernel */
+int hbec_glue_range_tile_bytes(void);
+/* test hook, as hbec_set_mixed_plan_chunk_tiles */
+int hbec_set_glue_range_chunk_tiles(uint64_t tiles);
+
 /* ecSplit (ecutils.go:26-72) for every entry of a plan in one call: the stabilize path of
  * a batch whose objects are in device memory, and the inverse of hbec_glue_plan_mixed.
  * Per stripe ecSplit reads k * S bytes of the object, zero-pads the last stripe to a
