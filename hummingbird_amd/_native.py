@@ -168,6 +168,12 @@ _SIG = [
     ("hbec_glue_range_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_glue_range_tile_bytes", C.c_int, []),
     ("hbec_set_glue_range_chunk_tiles", C.c_int, [C.c_uint64]),
+    ("hbec_etag_plan_mixed", C.c_int, [_P, _P, _U8P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P,
+                                       C.c_uint32, _P, _P, _P, _P]),
+    ("hbec_etag_plan_files", C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64,
+                                       _U8P, C.c_uint32, C.POINTER(C.c_uint32), _P, C.c_uint32, _P, _P, _P, _P]),
+    ("hbec_etag_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]),
     ("hbec_split_plan", C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64), _P]),
     ("hbec_split_plan_files", C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64,
                                         _P, _P]),

@@ -620,6 +620,88 @@ class StripePlan:
             patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d,
             st.ctypes.data_as(C.POINTER(C.c_uint64)), en.ctypes.data_as(C.POINTER(C.c_uint64)), _stream_ptr(stream)))
 
+    def _etag_tensors(self, n_slots, per, digests, expected, bad, filter):
+        """The shape and dtype checks of etag_mixed / etag_files."""
+        import torch
+
+        for name, t, need, what in (("bad", bad, n_slots, per), ("filter", filter, self._n, "stripe")):
+            if t is None:
+                continue
+            if t.dtype != torch.uint32 and t.dtype != torch.int32:
+                raise ValueError(f"{name} must be a 32-bit integer tensor")
+            if not t.is_cuda or not t.is_contiguous() or t.numel() < need:
+                raise ValueError(f"{name} must be a contiguous CUDA tensor with one entry per {what}")
+        for name, t in (("digests", digests), ("expected", expected)):
+            if t is None:
+                continue
+            if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.numel() < n_slots * 16:
+                raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor of 16 bytes per {per}")
+        if expected is not None and bad is None:
+            raise ValueError("expected needs bad")
+
+    def etag_mixed(self, present, lens, digests=None, expected=None, bad=None, filter=None, filter_bits=1,
+                   stream=None):
+        """The ETag check of every entry in one call (hbec_etag_plan_mixed): the
+        raw MD5 of entry i's data shards 0..k-1 back to back, their first
+        lens[i] bytes, hashed where they lie.  ``present`` is [n, k+m] as in
+        glue_mixed (None: every shard present): a missing data shard with a
+        byte below lens[i] is decoded into scratch first and read from there; no
+        shard and no object-sized buffer is written.  ``digests`` and
+        ``expected`` are uint8 CUDA tensors of n*16 bytes (at least one is
+        needed); ``bad`` and ``filter`` are 32-bit CUDA tensors with one word
+        per entry: bad[i] |= 1 where the digest differs from ``expected``
+        (caller-zeroed, needed with ``expected``), and only entries with
+        filter[i] & filter_bits are examined (None: all).  lens[i] = 0 skips the
+        entry; lens[i] <= k * S_i.  After a repair, a rebuilt data shard has no
+        stored ShardHash; the stored ETag is its check: repair_mixed, then
+        etag_mixed(None, lens, expected=etags, bad=bad) on one stream."""
+        import numpy as np
+
+        n = self.enc.DataShards + self.enc.ParityShards
+        self._etag_tensors(self._n, "stripe", digests, expected, bad, filter)
+        patterns, pattern_of = self._patterns(np.ones((self._n, n), bool) if present is None else present)
+        if len(lens) != self._n:
+            raise ValueError("lens needs one element per entry")
+        ln = np.zeros(max(1, self._n), np.uint64)
+        ln[:self._n] = [int(x) for x in lens]
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+
+        check(N.lib().hbec_etag_plan_mixed(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), ln.ctypes.data_as(C.POINTER(C.c_uint64)), ptr(filter),
+            int(filter_bits) & 0xFFFFFFFF, ptr(expected), ptr(digests), ptr(bad), _stream_ptr(stream)))
+
+    def etag_files(self, present, digests=None, expected=None, bad=None, filter=None, filter_bits=1, stream=None):
+        """etag_mixed for a ``files=`` plan, object by object
+        (hbec_etag_plan_files): the ETag of object g, the MD5 of the bytes
+        glue_files would write for it, its stripes hashed as one stream.
+        ``digests`` and ``expected`` hold n_objects*16 bytes and ``bad`` one
+        word per object; ``present`` and ``filter`` stay per ENTRY, and an
+        object is hashed when any of its entries passes the filter.  The
+        lengths are the plan's; an object with no byte is left untouched."""
+        import numpy as np
+
+        if getattr(self, "_content_lengths", None) is None:
+            raise ValueError("etag_files needs a plan built from files=")
+        n = self.enc.DataShards + self.enc.ParityShards
+        n_obj = len(self._content_lengths)
+        self._etag_tensors(n_obj, "object", digests, expected, bad, filter)
+        patterns, pattern_of = self._patterns(np.ones((self._n, n), bool) if present is None else present)
+        ln = np.zeros(max(1, n_obj), np.uint64)
+        ln[:n_obj] = self._content_lengths
+        starts = np.ascontiguousarray(self.object_start, dtype=np.uint32)
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+
+        check(N.lib().hbec_etag_plan_files(
+            self.enc.handle, self._h, starts.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
+            ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), patterns.ctypes.data_as(N._U8P),
+            patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), ptr(filter),
+            int(filter_bits) & 0xFFFFFFFF, ptr(expected), ptr(digests), ptr(bad), _stream_ptr(stream)))
+
     def split(self, srcs, lens, stream=None):
         """ecSplit for every entry in one call (hbec_split_plan), the inverse
         of glue_mixed: the lens[i] bytes at the device address srcs[i] (any
@@ -694,6 +776,17 @@ def glue_range_tile_bytes() -> int:
 def set_glue_range_chunk_tiles(tiles: int) -> None:
     """Test hook: range kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_glue_range_chunk_tiles(int(tiles)))
+
+
+def etag_plan_stats():
+    """Since load, for StripePlan.etag_mixed / etag_files: launches of the chain
+    kernel md5_etag (`kernel_launches`), chains listed, one per object with a
+    byte in it (`chains`), the segments those chains walk as the host lists
+    them (`segments`), and the entries of which any missing data byte was
+    decoded beforehand (`decoded_entries`)."""
+    a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_etag_plan_stats(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return {"kernel_launches": a.value, "chains": b.value, "segments": c.value, "decoded_entries": d.value}
 
 
 def split_plan_stats():

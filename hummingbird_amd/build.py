@@ -20,8 +20,8 @@ LIB = PKG / "libhbec.so"
 ROOT = PKG.parent
 INCLUDE = ROOT / "include"
 
-SOURCES = ["odd_k912.hip", "odd_k58.hip", "odd_bp.hip", "kernels.hip", "odd.hip", "wide.hip", "stripes.hip", "mixed.hip", "mixedplan.hip", "vmixed.hip", "locate.hip", "repair.hip", "heal.hip", "hashplan.hip", "hashfiles.hip", "glue.hip", "gluerange.hip", "splitplan.hip", "verify.hip", "vplan.hip", "md5.hip", "shardhash.cpp", "hbec.cpp", "ecutils.cpp", "plan.cpp", "plan_calls.cpp", "hostpath.cpp", "batcher.cpp", "coalesce.cpp"]
-HEADERS = ["kernels.h", "gf256.h", "internal.h", "gf_device.h", "pool.h", "odd_impl.h", "tuning.h", "xor_sched.h", "mixed.h", "vplan.h", "mixedplan.h", "planwalk.h", "plan_internal.h", "vmixed.h", "locate.h", "repair.h", "repair_tile.h", "heal.h", "hashplan.h", "hashfiles.h", "hostcut.h", "md5_device.h", "unaligned_tile.h", "shard_rows.h", "shardplan.h", "glue.h", "glue_tile.h", "gluerange.h", "gluerange_tile.h", "splitplan.h", "split_tile.h", "hashplan_kernel.inc", "hashfiles_kernel.inc"]
+SOURCES = ["odd_k912.hip", "odd_k58.hip", "odd_bp.hip", "kernels.hip", "odd.hip", "wide.hip", "stripes.hip", "mixed.hip", "mixedplan.hip", "vmixed.hip", "locate.hip", "repair.hip", "heal.hip", "hashplan.hip", "hashfiles.hip", "glue.hip", "gluerange.hip", "etag.hip", "splitplan.hip", "verify.hip", "vplan.hip", "md5.hip", "shardhash.cpp", "hbec.cpp", "ecutils.cpp", "plan.cpp", "plan_calls.cpp", "hostpath.cpp", "batcher.cpp", "coalesce.cpp"]
+HEADERS = ["kernels.h", "gf256.h", "internal.h", "gf_device.h", "pool.h", "odd_impl.h", "tuning.h", "xor_sched.h", "mixed.h", "vplan.h", "mixedplan.h", "planwalk.h", "plan_internal.h", "vmixed.h", "locate.h", "repair.h", "repair_tile.h", "heal.h", "hashplan.h", "hashfiles.h", "hostcut.h", "md5_device.h", "unaligned_tile.h", "shard_rows.h", "shardplan.h", "glue.h", "glue_tile.h", "gluerange.h", "gluerange_tile.h", "splitplan.h", "split_tile.h", "hashplan_kernel.inc", "hashfiles_kernel.inc", "etag.h", "etag_kernel.inc"]
 ARCH = os.environ.get("HBEC_OFFLOAD_ARCH", "gfx950")
 
 

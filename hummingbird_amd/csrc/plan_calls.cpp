@@ -19,7 +19,10 @@
 // hbec_split_plan_files; splitplan.h, splitplan.hip), walks them too and stages
 // a source per entry.  Any byte range of every entry (hbec_glue_plan_range and
 // hbec_glue_plan_files_range; gluerange.h, gluerange.hip) is the glue call with a
-// start beside each length.
+// start beside each length.  The ETag of every object (hbec_etag_plan_mixed and
+// hbec_etag_plan_files; etag.h, etag.hip) decodes what is missing through that
+// call into scratch and hashes the object bytes where they lie, on the hash
+// calls' records.
 // All of them stage and launch through staged_launches; plan.cpp builds the plans.
 #include <hip/hip_runtime.h>
 
@@ -33,6 +36,7 @@
 #include <vector>
 
 #include "../../include/hbec.h"
+#include "etag.h"
 #include "gf256.h"
 #include "glue.h"
 #include "gluerange.h"
@@ -59,7 +63,7 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
     std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal); chains (hash calls)
@@ -67,6 +71,7 @@ struct CallSlot {
 };
 CallSlot g_calls[kCalls];
 std::atomic<uint64_t> g_hashfiles_segments{0};
+std::atomic<uint64_t> g_etag_segments{0}, g_etag_decoded{0};  // hbec_etag_plan_stats' third and fourth
 
 void count(std::atomic<uint64_t>& c, uint64_t n = 1) { c.fetch_add(n, std::memory_order_relaxed); }
 
@@ -959,6 +964,35 @@ int glue_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* pat
 
 // ---- whole objects of a files plan from their shard files (hbec_glue_plan_files) ----
 
+// What hbec_glue_plan_files checks of the object table, the chunk size and the
+// content lengths of a plan with entries, and the cut of every object into its
+// entries: each(g, i, off, len) for entry i of object g, which holds the
+// object's bytes [off, off + len).  hbec_etag_plan_files takes the same checks.
+template <class Each>
+int files_cut_entries(const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                      const uint64_t* content_lengths, uint64_t chunk_size, Each&& each) {
+    const int k = plan->k;
+    if (const char* why = hbec::files_check_objects(object_start, n_objects, plan->n_src))
+        return fail(HBEC_ERR_INVALID_ARG, why);
+    if (chunk_size == 0 || chunk_size > (uint64_t)INT64_MAX) return fail(HBEC_ERR_INVALID_ARG, "chunk_size out of range");
+    for (uint32_t g = 0; g < n_objects; ++g) {
+        const uint64_t L = content_lengths[g], cnt = object_start[g + 1] - object_start[g];
+        if (L > (uint64_t)INT64_MAX || hbec::ec_stripe_count((int64_t)L, k, (int64_t)chunk_size) != cnt)
+            return fail(HBEC_ERR_INVALID_ARG, "content length does not give the entry count (object " +
+                                                  std::to_string(g) + ")");
+        for (uint64_t t = 0; t < cnt; ++t) {
+            const uint64_t i = object_start[g] + t;
+            if (plan->src[i].shard_len != hbec::ec_stripe_shard_length((int64_t)L, k, (int64_t)chunk_size, t))
+                return fail(HBEC_ERR_INVALID_ARG, "shard length mismatch (object " + std::to_string(g) +
+                                                      ", stripe " + std::to_string(t) + ")");
+            uint64_t off = 0, len = 0;
+            hbec::glue_files_cut(L, (uint64_t)k, chunk_size, t, &off, &len);
+            each(g, i, off, len);
+        }
+    }
+    return HBEC_OK;
+}
+
 int glue_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
                     const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
                     uint32_t n_patterns, const uint32_t* pattern_of, void* const* object_dsts, hipStream_t stream) {
@@ -969,24 +1003,13 @@ int glue_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* ob
     std::vector<void*> dsts((size_t)std::max<uint64_t>(1, n_src), nullptr);
     std::vector<uint64_t> lens((size_t)std::max<uint64_t>(1, n_src), 0u);
     if (n_src) {
-        if (const char* why = hbec::files_check_objects(object_start, n_objects, n_src))
-            return fail(HBEC_ERR_INVALID_ARG, why);
-        if (chunk_size == 0 || chunk_size > (uint64_t)INT64_MAX) return fail(HBEC_ERR_INVALID_ARG, "chunk_size out of range");
-        for (uint32_t g = 0; g < n_objects; ++g) {
-            const uint64_t L = content_lengths[g], cnt = object_start[g + 1] - object_start[g];
-            if (L > (uint64_t)INT64_MAX || hbec::ec_stripe_count((int64_t)L, k, (int64_t)chunk_size) != cnt)
-                return fail(HBEC_ERR_INVALID_ARG, "content length does not give the entry count (object " +
-                                                      std::to_string(g) + ")");
-            for (uint64_t t = 0; t < cnt; ++t) {
-                const uint64_t i = object_start[g] + t;
-                if (plan->src[i].shard_len != hbec::ec_stripe_shard_length((int64_t)L, k, (int64_t)chunk_size, t))
-                    return fail(HBEC_ERR_INVALID_ARG, "shard length mismatch (object " + std::to_string(g) +
-                                                          ", stripe " + std::to_string(t) + ")");
-                uint64_t off = 0;
-                hbec::glue_files_cut(L, (uint64_t)k, chunk_size, t, &off, &lens[i]);
-                dsts[i] = object_dsts[g] ? static_cast<uint8_t*>(object_dsts[g]) + off : nullptr;
-            }
-        }
+        const int rc = files_cut_entries(plan, object_start, n_objects, content_lengths, chunk_size,
+                                         [&](uint32_t g, uint64_t i, uint64_t off, uint64_t len) {
+                                             lens[i] = len;
+                                             dsts[i] = object_dsts[g] ? static_cast<uint8_t*>(object_dsts[g]) + off
+                                                                      : nullptr;
+                                         });
+        if (rc) return rc;
     }
     return glue_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), lens.data(), stream);
 }
@@ -1181,6 +1204,121 @@ int glue_plan_files_range(hbec_codec* codec, const hbec_plan* plan, const uint32
     }
     return glue_plan_range(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), starts.data(), lens.data(),
                            stream);
+}
+
+// ---- the ETag of every object from its shards (hbec_etag_plan_mixed, hbec_etag_plan_files) ----
+
+// Both ETag calls after the checks of their own.  lens: the bytes of D hashed,
+// per source entry; object_start: the chains' entries (nullptr: every entry is
+// an object of its own).  The call decodes first, then hashes: the span of
+// every entry with a missing data shard below its length (etag.h) goes through
+// hbec_glue_plan_range into one scratch allocation, on the same stream, and the
+// chain kernel reads it there.  The span is decoded whether or not the entry
+// passes the device-side filter: the host cannot know.
+int etag_plan(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+              const uint32_t* pattern_of, const uint64_t* lens, const uint32_t* object_start, uint32_t n_objects,
+              const uint32_t* d_filter, uint32_t filter_bits, const uint8_t* d_expected, uint8_t* d_digests,
+              uint32_t* d_bad, hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    if (!lens) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    if (d_expected && !d_bad) return fail(HBEC_ERR_INVALID_ARG, "d_expected needs d_bad");
+    if (d_bad && d_bad == d_filter) return fail(HBEC_ERR_INVALID_ARG, "d_bad and d_filter must be distinct");
+    if ((reinterpret_cast<uintptr_t>(d_digests) | reinterpret_cast<uintptr_t>(d_expected)) & 3u)
+        return fail(HBEC_ERR_INVALID_ARG, "digest buffer not 4-byte aligned");
+    const int k = plan->k, n = k + plan->m;
+    const uint64_t n_src = plan->n_src;
+    std::vector<hbec::ERec> erecs((size_t)n_src);
+    bool any = false;
+    for (uint64_t i = 0; i < n_src; ++i) {  // zero-length entries too
+        const uint64_t S = plan->src[i].shard_len;
+        if ((unsigned __int128)lens[i] > (unsigned __int128)S * (uint64_t)k)
+            return fail(HBEC_ERR_INVALID_ARG, "lens exceeds k * shard_len (entry " + std::to_string(i) + ")");
+        erecs[i] = hbec::ERec{lens[i], 0u, 0u, 0u};
+        any = any || lens[i];
+    }
+    if (!any) return HBEC_OK;  // no chain
+    if (!d_digests && !d_expected) return fail(HBEC_ERR_INVALID_ARG, "neither d_digests nor d_expected given");
+    std::vector<hbec::EChain> chains;
+    hbec::etag_chains(erecs, object_start, object_start ? n_objects : (uint32_t)n_src, chains);
+    if (chains.size() / 64 >= (1ull << 31)) return fail(HBEC_ERR_INVALID_ARG, "call too large (>= 2^37 chains)");
+    rc = hash_plan_device(plan);
+    if (rc) return rc;
+
+    // the spans to decode, back to back in one scratch allocation
+    std::vector<void*> dsts((size_t)n_src, nullptr);
+    std::vector<uint64_t> starts((size_t)n_src, 0u), span((size_t)n_src, 0u);
+    uint64_t scratch_bytes = 0, decoded = 0;
+    for (uint64_t i = 0; i < n_src; ++i) {
+        hbec::ERec& r = erecs[i];
+        const uint64_t S = plan->src[i].shard_len;
+        if (!r.len || !hbec::etag_span((uint32_t)k, S, r.len, patterns + (size_t)pattern_of[i] * n, &r.j0, &r.j1))
+            continue;
+        starts[i] = hbec::etag_span_lo(S, r.j0);
+        span[i] = hbec::etag_span_hi(S, r.len, r.j1) - starts[i];
+        r.red = 1u;  // its place in scratch, below
+        scratch_bytes += span[i];
+        ++decoded;
+    }
+    void* scratch = nullptr;
+    if (decoded) {
+        // whole dwords: the chain kernel loads the dword a byte lies in
+        rc = hbec::scratch_alloc((size_t)((scratch_bytes + 3u) & ~(uint64_t)3u), stream, &scratch);
+        if (rc) return rc;
+        uint64_t at = reinterpret_cast<uintptr_t>(scratch);
+        for (uint64_t i = 0; i < n_src; ++i) {
+            if (!erecs[i].red) continue;
+            dsts[i] = reinterpret_cast<void*>(at);
+            erecs[i].red = at - starts[i];
+            at += span[i];
+        }
+        rc = glue_plan_range(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), starts.data(), span.data(),
+                             stream);
+        if (rc) {
+            hbec::scratch_free(scratch, stream);
+            return rc;
+        }
+    }
+    uint64_t segments = 0;
+    for (uint64_t i = 0; i < n_src; ++i)
+        segments += hbec::etag_entry_segments(plan->shards, (uint32_t)k, plan->src[i].shard_len, erecs[i]);
+
+    static_assert(sizeof(hbec::EChain) == 24 && sizeof(hbec::ERec) == 24, "staged as words, 8-byte aligned");
+    const size_t chain_words = chains.size() * (sizeof(hbec::EChain) / 4);
+    std::vector<uint32_t> stage(chain_words + erecs.size() * (sizeof(hbec::ERec) / 4));
+    std::memcpy(stage.data(), chains.data(), chain_words * 4);
+    std::memcpy(stage.data() + chain_words, erecs.data(), erecs.size() * sizeof(hbec::ERec));
+    rc = staged_launches(plan, stage, stream, [&](const uint32_t* d_stage) {
+        count(g_calls[kEtag].launches);
+        count(g_calls[kEtag].second, chains.size());
+        count(g_etag_segments, segments);
+        count(g_etag_decoded, decoded);
+        const hipError_t e = (hipError_t)hbec::launch_etag_chains(
+            plan->d_hrecs, reinterpret_cast<const hbec::ERec*>(d_stage + chain_words),
+            reinterpret_cast<const hbec::EChain*>(d_stage), chains.size(), k, d_filter, filter_bits, d_expected,
+            d_digests, d_expected ? d_bad : nullptr, stream, plan->shards);
+        return Queued{e, "launch md5_etag"};
+    });
+    hbec::scratch_free(scratch, stream);
+    return rc;
+}
+
+int etag_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                    const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
+                    uint32_t n_patterns, const uint32_t* pattern_of, const uint32_t* d_filter, uint32_t filter_bits,
+                    const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad, hipStream_t stream) {
+    if (!codec || !plan || !content_lengths) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
+    std::vector<uint64_t> lens((size_t)std::max<uint64_t>(1, plan->n_src), 0u);
+    if (plan->n_src) {
+        const int rc = files_cut_entries(plan, object_start, n_objects, content_lengths, chunk_size,
+                                         [&](uint32_t, uint64_t i, uint64_t, uint64_t len) { lens[i] = len; });
+        if (rc) return rc;
+    }
+    return etag_plan(codec, plan, patterns, n_patterns, pattern_of, lens.data(), plan->n_src ? object_start : nullptr,
+                     n_objects, d_filter, filter_bits, d_expected, d_digests, d_bad, stream);
 }
 
 // ---- the k + m shards of every entry from its object bytes (hbec_split_plan) ----
@@ -1521,6 +1659,39 @@ int hbec_glue_range_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
 
 int hbec_set_glue_range_chunk_tiles(uint64_t tiles) {
     return set_chunk_tiles("hbec_set_glue_range_chunk_tiles", kGlueRange, tiles);
+}
+
+int hbec_etag_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                         const uint32_t* pattern_of, const uint64_t* lens, const uint32_t* d_filter,
+                         uint32_t filter_bits, const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad,
+                         void* hip_stream) {
+    return hbec::guarded("hbec_etag_plan_mixed", [&]() -> int {
+        return etag_plan(codec, plan, patterns, n_patterns, pattern_of, lens, nullptr, 0, d_filter, filter_bits,
+                         d_expected, d_digests, d_bad, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_etag_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                         const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
+                         uint32_t n_patterns, const uint32_t* pattern_of, const uint32_t* d_filter,
+                         uint32_t filter_bits, const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad,
+                         void* hip_stream) {
+    return hbec::guarded("hbec_etag_plan_files", [&]() -> int {
+        return etag_plan_files(codec, plan, object_start, n_objects, content_lengths, chunk_size, patterns,
+                               n_patterns, pattern_of, d_filter, filter_bits, d_expected, d_digests, d_bad,
+                               static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_etag_plan_stats(uint64_t* kernel_launches, uint64_t* chains, uint64_t* segments, uint64_t* decoded_entries) {
+    // a null third or fourth fails with the other two: call_stats sees a null `chains`
+    const int rc = call_stats("hbec_etag_plan_stats", kEtag, kernel_launches,
+                              segments && decoded_entries ? chains : nullptr);
+    if (rc == HBEC_OK) {
+        *segments = g_etag_segments.load(std::memory_order_relaxed);
+        *decoded_entries = g_etag_decoded.load(std::memory_order_relaxed);
+    }
+    return rc;
 }
 
 int hbec_split_plan(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,

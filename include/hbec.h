@@ -790,6 +790,75 @@ int hbec_glue_range_tile_bytes(void);
 /* test hook, as hbec_set_mixed_plan_chunk_tiles */
 int hbec_set_glue_range_chunk_tiles(uint64_t tiles);
 
+/* The ETag of every entry of a plan from its shards, degraded or not: the MD5 of the object's
+ * own bytes, which every shard carries in its metadata (ecengine.go:320-321,
+ * indexdb.go:739-740,768-769, ecobj.go:415-417) and the reference's auditor checks for
+ * unstabilized objects (auditor.go:122-127).  A shard's ShardHash is held only by the node that
+ * stores the shard (indexdb.go:746-753, auditor.go:129), so after a lost data shard has been
+ * rebuilt nothing stored says what its ShardHash should be: the ETag is the one digest that
+ * survives a lost node.  patterns / n_patterns / pattern_of: host arrays exactly as in
+ * hbec_glue_plan_mixed, with its checks, precedence and messages.  lens: host array, one
+ * element per source entry (zero-length entries included), copied before the call returns.
+ * With D_i entry i's data shards 0..k-1 back to back as hbec_glue_plan_mixed defines it
+ * (ecutils.go:171-183; a present data shard as it lies, a missing one what ReconstructData,
+ * ecutils.go:168, computes from the entry's first k present shards), the raw MD5 of
+ * D_i[0, lens[i]) is written to d_digests + 16 i (uint8, device, 4-byte aligned, may be NULL;
+ * only the 16 bytes of an examined entry are written) and compared with d_expected + 16 i
+ * (likewise, may be NULL; needs d_bad): d_bad[i] |= 1 where they differ.  d_bad: uint32,
+ * device, one word per source entry, caller-zeroed, only ever ORed into.  lens[i] = 0 skips
+ * the entry and leaves its slots untouched; otherwise lens[i] <= k * S_i.  Entry i is examined
+ * when d_filter is NULL or d_filter[i] & filter_bits (uint32, device, read on the device;
+ * nothing is copied back).  Bytes of D_i at or beyond lens[i], ecSplit's pad or whatever lies
+ * there, are never hashed; a missing data shard with no byte below lens[i] is never decoded,
+ * and missing parity never matters.
+ * The bytes are hashed where they lie, one lane per chain as hbec_hash_plan_files: no shard is
+ * written and no object-sized buffer is needed.  Before the chain kernel the call decodes, on
+ * the same stream and through hbec_glue_plan_range, the SPAN of every entry with a missing
+ * data shard below its length: D_i from that entry's first such shard to the end of its last
+ * one (or lens[i]), into stream-ordered scratch of at most that span summed over entries;
+ * present shards between the two are copied along, and the chain reads the span there.  The
+ * host cannot see d_filter, so the span of an entry the filter then excludes is decoded all
+ * the same.  On a stripe or object plan a run of present data shards is contiguous and is
+ * walked as one segment; on a shards plan each shard is one.
+ * Errors, all found before anything is queued or written: hbec_glue_plan_mixed's pattern
+ * errors first (HBEC_ERR_TOO_FEW_SHARDS for a listed pattern with fewer than k present among
+ * them); then, all HBEC_ERR_INVALID_ARG: a null lens; d_expected without d_bad; d_bad ==
+ * d_filter; a digest buffer that is not 4-byte aligned; lens[i] > k * S_i, named by entry;
+ * and for a call with a chain neither d_digests nor d_expected.  Scratch exhaustion is
+ * HBEC_ERR_NOMEM with nothing queued.  A plan with no entries, or a call with every lens 0,
+ * accepts null device pointers and launches nothing.
+ * One lane hashes one chain and MD5 is serial, so a call lasts at least as long as its longest
+ * examined chain.  Any plan kind and any (k, m) the plan accepts; the decode is one launch for
+ * k <= 12 with m <= 4 and goes per entry for other shapes, as hbec_glue_plan_range says.
+ * Queued on hip_stream and not waited for; calls on one plan take turns with the other
+ * hbec_*_plan_mixed calls. */
+int hbec_etag_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                         const uint32_t* pattern_of, const uint64_t* lens, const uint32_t* d_filter,
+                         uint32_t filter_bits, const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad,
+                         void* hip_stream);
+/* The object-level form, the ETag itself (ecengine.go:320-321) of objects of more than one
+ * stripe: object g is the entries [object_start[g], object_start[g + 1]), and its chain is
+ * those entries' D in stripe order (ecutils.go:171-183), cut to content_lengths[g] exactly as
+ * hbec_glue_plan_files cuts the object into its entries, hashed as ONE stream: one pad, a
+ * 64-bit bit length.  That is the MD5 of the bytes hbec_glue_plan_files would write.  The
+ * digest goes to d_digests + 16 g, the comparison reads d_expected + 16 g, and d_bad[g] |= 1:
+ * one slot and one word per OBJECT.  patterns / pattern_of stay per ENTRY (a file can fail
+ * between two stripes) and so does d_filter: an object is examined when any of its entries
+ * passes, as in hbec_hash_plan_files.  An object with no byte has no chain and its slots stay
+ * untouched (its ETag is the MD5 of nothing).  Errors: hbec_glue_plan_files's of the codec,
+ * the plan, content_lengths, object_start, chunk_size and the content lengths, with its
+ * messages; then hbec_etag_plan_mixed's.  Everything else as hbec_etag_plan_mixed. */
+int hbec_etag_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                         const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
+                         uint32_t n_patterns, const uint32_t* pattern_of, const uint32_t* d_filter,
+                         uint32_t filter_bits, const uint8_t* d_expected, uint8_t* d_digests, uint32_t* d_bad,
+                         void* hip_stream);
+/* since load: launches of the chain kernel (md5_etag), chains listed, segments those chains
+ * walk as the host lists them (one per run of present data shards on stripe and object plans,
+ * one per shard on shards plans, one per decoded span), and entries of which any missing data
+ * byte was decoded */
+int hbec_etag_plan_stats(uint64_t* kernel_launches, uint64_t* chains, uint64_t* segments, uint64_t* decoded_entries);
+
 /* ecSplit (ecutils.go:26-72) for every entry of a plan in one call: the stabilize path of
  * a batch whose objects are in device memory, and the inverse of hbec_glue_plan_mixed.
  * Per stripe ecSplit reads k * S bytes of the object, zero-pads the last stripe to a
