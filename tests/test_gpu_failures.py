@@ -45,6 +45,36 @@ def test_pinned_host_alloc_failure_is_nomem_and_recovers():
     _encode_ok(RS.New(4, 2), 4, 2, seed=1)
 
 
+def _fill_hbm():
+    """Tensors that hold HBM until an allocation of 256 MiB has been refused,
+    less 128 MiB given back for the calls that must still work: at most
+    384 MiB can then be allocated.  The free figure of mem_get_info alone
+    does not promise that: with 758 MiB reported free after the first tensor
+    below, 1 GiB more has been had from the driver in 256 MiB pieces."""
+    torch.cuda.empty_cache()  # or torch hands its cache back at the refusal below
+    spare = torch.empty(128 << 20, dtype=torch.uint8, device="cuda")
+    free, _ = torch.cuda.mem_get_info()
+    hogs = []
+    for slack in (256 << 20, 512 << 20, 768 << 20):
+        try:
+            hogs.append(torch.empty(free - slack, dtype=torch.uint8, device="cuda"))
+            break
+        except RuntimeError:
+            continue
+    assert hogs, "could not fill HBM for the test"
+    refused = False
+    for _ in range(64):  # 16 GiB: far more than the free figure has been seen to be off by
+        try:
+            hogs.append(torch.empty(256 << 20, dtype=torch.uint8, device="cuda"))
+        except RuntimeError:
+            refused = True
+            break
+    assert refused, "HBM still gives 256 MiB, 16 GiB past what it reported free"
+    del spare
+    torch.cuda.empty_cache()
+    return hogs
+
+
 def test_device_oom_is_nomem_and_next_call_succeeds():
     """A stripe plan's tile records live in HBM (hbec_plan_stripes, one 32-B
     record per tile).  With HBM nearly full, a plan whose records need 1 GiB
@@ -73,15 +103,7 @@ def test_device_oom_is_nomem_and_next_call_succeeds():
     # HBM (the plan only records addresses; it is never run)
     big = [(small.data_ptr() - (small.data_ptr() % 256), 64 << 20)] * 512
 
-    free, _ = torch.cuda.mem_get_info()
-    hog = None
-    for slack in (256 << 20, 512 << 20, 768 << 20):  # leave less than the plan's 1 GiB
-        try:
-            hog = torch.empty(free - slack, dtype=torch.uint8, device="cuda")
-            break
-        except RuntimeError:
-            continue
-    assert hog is not None, "could not fill HBM for the test"
+    hog = _fill_hbm()  # leaves less than the plan's 1 GiB
     try:
         with pytest.raises(RS.ErrNoMem):
             B.StripePlan(e42, big)
