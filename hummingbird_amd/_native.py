@@ -35,6 +35,11 @@ LOC_CLEAN = -1
 LOC_AMBIGUOUS = -2
 LOC_MULTIPLE = -3
 LOC_UNCHECKED = -4
+# bits of a word of hbec_correct_plan_mixed (bits 0..15: the shards corrected)
+COR_BAD = 0x80000000
+COR_SKIPPED = 0x40000000
+COR_NOTHING = 0x20000000
+COR_LEFT = 0x10000000
 # flag bits of hbec_heal_plan_mixed beside hbec_repair_plan_mixed's 1 and 2
 HEAL_DONE = 4
 HEAL_UNNAMED = 8
@@ -139,6 +144,10 @@ _SIG = [
     ("hbec_locate_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_locate_plan_tile_bytes", C.c_int, []),
     ("hbec_set_locate_plan_chunk_tiles", C.c_int, [C.c_uint64]),
+    ("hbec_correct_plan_mixed", C.c_int, [_P, _P, _U8P, C.c_uint32, C.POINTER(C.c_uint32), _P, _P, _P]),
+    ("hbec_correct_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_correct_plan_tile_bytes", C.c_int, []),
+    ("hbec_set_correct_plan_chunk_tiles", C.c_int, [C.c_uint64]),
     ("hbec_repair_plan_mixed", C.c_int, [_P, _P, _U8P, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, _P, _P]),
     ("hbec_repair_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_repair_plan_tile_bytes", C.c_int, []),

@@ -365,6 +365,50 @@ class StripePlan:
             None if flags is None else C.c_void_p(flags.data_ptr()), C.c_void_p(where.data_ptr()),
             _stream_ptr(stream)))
 
+    def correct_mixed(self, present, fixed, flags=None, stream=None):
+        """Correct the corrupt bytes of every inconsistent entry column by
+        column, in place: at every byte position whose syndrome names one shard
+        (two or more checked shards needed) that shard's byte is XORed with the
+        error, one byte and nothing else, so two shards that went bad at
+        different offsets are both repaired where heal_mixed must refuse.
+        ``present`` as in locate_mixed (None: every shard present); ``fixed`` a
+        caller-zeroed 32-bit CUDA tensor with one word per entry that is ORed
+        into: COR_BAD, COR_SKIPPED, COR_NOTHING, COR_LEFT (some inconsistent
+        position had no candidate and was left as it is) and, in bits 0..15, the
+        shards with a byte corrected (hbec_correct_plan_mixed).  An entry is
+        fully corrected when COR_BAD is set and COR_LEFT is clear.  ``flags``:
+        the tensor verify_mixed filled under the same masks; only entries with
+        bit 0 set are read.  None: every entry is examined.  Missing shards are
+        not written: a sweep is verify_mixed, correct_mixed(flags=flags),
+        repair_mixed, etag_mixed, queued on one stream."""
+        import numpy as np
+        import torch
+
+        n = self.enc.DataShards + self.enc.ParityShards
+        for name, t in (("fixed", fixed), ("flags", flags)):
+            if t is None and name == "flags":
+                continue
+            if t.dtype != torch.uint32 and t.dtype != torch.int32:
+                raise ValueError(f"{name} must be a 32-bit integer tensor")
+            if not t.is_cuda or not t.is_contiguous() or t.numel() < self._n:
+                raise ValueError(f"{name} must be a contiguous CUDA tensor with one entry per stripe")
+        if flags is not None and flags.data_ptr() == fixed.data_ptr() and self._n:
+            raise ValueError("fixed must not alias flags")
+        p = np.ones((self._n, n), bool) if present is None else np.asarray(present) != 0
+        if p.ndim != 2 or p.shape[0] != self._n or p.shape[1] != n:
+            raise ValueError("present must be [n_stripes, k+m]")
+        if self._n == 0:
+            patterns, pattern_of = p.astype(np.uint8), np.zeros(0, np.uint32)
+        else:
+            patterns, pattern_of = np.unique(p.astype(np.uint8), axis=0, return_inverse=True)
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        pattern_of = np.ascontiguousarray(pattern_of.reshape(-1), dtype=np.uint32)
+        check(N.lib().hbec_correct_plan_mixed(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)),
+            None if flags is None else C.c_void_p(flags.data_ptr()), C.c_void_p(fixed.data_ptr()),
+            _stream_ptr(stream)))
+
     def heal_mixed(self, present, where, flags, stream=None):
         """Act on locate_mixed's answer on this plan, with nothing copied back:
         every entry whose word of ``where`` names one shard is repaired again
@@ -866,6 +910,25 @@ def locate_plan_tile_bytes() -> int:
 def set_locate_plan_chunk_tiles(tiles: int) -> None:
     """Test hook: locate kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_locate_plan_chunk_tiles(int(tiles)))
+
+
+def correct_plan_stats():
+    """Since load, for StripePlan.correct_mixed: launches of the correct kernel
+    (`kernel_launches`) and entries of a shape it does not take, marked
+    COR_SKIPPED (`skipped_entries`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_correct_plan_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "skipped_entries": b.value}
+
+
+def correct_plan_tile_bytes() -> int:
+    """Shard bytes per wave tile of the correct kernel."""
+    return int(N.lib().hbec_correct_plan_tile_bytes())
+
+
+def set_correct_plan_chunk_tiles(tiles: int) -> None:
+    """Test hook: correct kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_correct_plan_chunk_tiles(int(tiles)))
 
 
 def repair_plan_stats():

@@ -7,6 +7,8 @@
 // (hbec_locate_plan_mixed; locate.h, locate.hip), the call that rebuilds and
 // checks in one pass (hbec_repair_plan_mixed; repair.h, repair.hip) and the call
 // that rebuilds the shard locate named (hbec_heal_plan_mixed; heal.h, heal.hip).
+// The call that corrects bad bytes column by column (hbec_correct_plan_mixed;
+// correct.h, correct.hip) walks them too, with records of its own.
 // The ShardHash audit of a plan (hbec_hash_plan_mixed; hashplan.h, hashplan.hip)
 // has records of its own with 64-bit lengths, built on first use likewise, and
 // stages its chain list where those calls stage their words.  The hash of
@@ -36,6 +38,7 @@
 #include <vector>
 
 #include "../../include/hbec.h"
+#include "correct.h"
 #include "etag.h"
 #include "gf256.h"
 #include "glue.h"
@@ -63,10 +66,10 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
-    std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal); chains (hash calls)
+    std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal, correct); chains (hash calls)
     std::atomic<uint64_t> chunk_tiles{0};  // test hook (hbec_set_*_chunk_tiles): tiles per launch of the walk kernel
 };
 CallSlot g_calls[kCalls];
@@ -584,6 +587,64 @@ int locate_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* p
     for (uint32_t i : plan->mp_other) {
         count(g_calls[kLocate].second);
         const hipError_t e = hbec::launch_vm_or(d_where + i, hbec::kLocSkipped, stream);
+        if (e != hipSuccess) return hip_fail(e, "launch gf_vm_or");
+    }
+    return HBEC_OK;
+}
+
+// ---- correct the corrupt bytes column by column (hbec_correct_plan_mixed) ----
+
+static_assert(HBEC_COR_BAD == hbec::kCorBad && HBEC_COR_SKIPPED == hbec::kCorSkipped &&
+                  HBEC_COR_NOTHING == hbec::kCorNothing && HBEC_COR_LEFT == hbec::kCorLeft,
+              "include/hbec.h and correct.h disagree");
+
+int correct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                       const uint32_t* pattern_of, const uint32_t* d_flags, uint32_t* d_fixed, hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    if (!d_fixed && plan->n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    if (d_fixed && d_fixed == d_flags) return fail(HBEC_ERR_INVALID_ARG, "d_fixed aliases d_flags");
+    const int k = plan->k, m = plan->m;
+    bool used = false;
+    rc = resolve_patterns(codec, patterns, false, false, true, pats, &used);
+    if (rc) return rc;
+    if (!used) return HBEC_OK;  // zero-length entries only
+    rc = mixed_plan_device(plan);
+    if (rc) return rc;
+
+    if (plan->n_mtiles > 0) {
+        // Verify's words over records that also hold the tables of 1 / rows[0][t]
+        int rmax = 1;  // exactly-k entries alone: any instance sets their bit
+        std::vector<uint32_t> stage;
+        const size_t rec_words = stage_patterns(
+            plan, pats, pattern_of, stage,
+            [&](PlanPattern& pp) {
+                const ShardSet& c = pp.chk;
+                if (!c.idx.empty())
+                    pp.rec = hbec::cor_pattern(stage, k, c.surv.data(), c.idx.data(), (int)c.idx.size(), c.rows.data());
+            },
+            [&](uint64_t i, const PlanPattern& pp) {
+                if (hbec::cor_route(k, m, plan->src[i].shard_len) != hbec::kVmKernel) return 0u;
+                rmax = std::max(rmax, (int)pp.chk.idx.size());
+                return hbec::vm_word((int)pp.chk.idx.size(), pp.rec);
+            });
+        int cus = 0;
+        rc = current_cus(&cus);
+        if (rc) return rc;
+        rc = staged_launches(plan, stage, stream, [&](const uint32_t* d_pats) {
+            return walk_chunks(kCorrect, plan->n_mtiles, "launch gf_correct_mixed_plan", [&](uint64_t t0, uint32_t nt) {
+                return hbec::launch_correct_mixed_plan(k, rmax, plan->d_mrecs, plan->d_mtiles + t0, nt,
+                                                       d_pats + rec_words, d_pats, d_flags, d_fixed, cus, stream,
+                                                       plan->shards);
+            });
+        });
+        if (rc) return rc;
+    }
+    // the other route is not examined: said in the entry's word, and counted
+    for (uint32_t i : plan->mp_other) {
+        count(g_calls[kCorrect].second);
+        const hipError_t e = hbec::launch_vm_or(d_fixed + i, hbec::kCorSkipped, stream);
         if (e != hipSuccess) return hip_fail(e, "launch gf_vm_or");
     }
     return HBEC_OK;
@@ -1551,6 +1612,24 @@ int hbec_locate_plan_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
 
 int hbec_set_locate_plan_chunk_tiles(uint64_t tiles) {
     return set_chunk_tiles("hbec_set_locate_plan_chunk_tiles", kLocate, tiles);
+}
+
+int hbec_correct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                            const uint32_t* pattern_of, const uint32_t* d_flags, uint32_t* d_fixed, void* hip_stream) {
+    return hbec::guarded("hbec_correct_plan_mixed", [&]() -> int {
+        return correct_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, d_flags, d_fixed,
+                                  static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_correct_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries) {
+    return call_stats("hbec_correct_plan_stats", kCorrect, kernel_launches, skipped_entries);
+}
+
+int hbec_correct_plan_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
+
+int hbec_set_correct_plan_chunk_tiles(uint64_t tiles) {
+    return set_chunk_tiles("hbec_set_correct_plan_chunk_tiles", kCorrect, tiles);
 }
 
 int hbec_heal_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,

@@ -434,6 +434,51 @@ int hbec_locate_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries)
 int hbec_locate_plan_tile_bytes(void);
 /* test hook, as hbec_set_verify_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
 int hbec_set_locate_plan_chunk_tiles(uint64_t tiles);
+/* Correct the corrupt bytes of every inconsistent stripe column by column, in place: what a
+ * sweep does when hbec_locate_plan_mixed cannot name one shard (HBEC_LOC_MULTIPLE: two disks
+ * that each lost a sector at different offsets of the stripe), and a cheaper answer than
+ * hbec_heal_plan_mixed when it can, since only the bytes that were wrong are written.
+ * patterns / n_patterns / pattern_of / d_flags: exactly those of hbec_locate_plan_mixed, with
+ * the same filter and the same errors, found before anything is queued or written.
+ * d_fixed: uint32, device, one entry per source entry, zeroed by the caller; it is only ever
+ * ORed into, zero-length entries are never touched, and it must not alias d_flags.
+ *   bit 31     HBEC_COR_BAD      some compared byte of the entry was inconsistent
+ *   bit 30     HBEC_COR_SKIPPED  the entry was not examined (the other route, below)
+ *   bit 29     HBEC_COR_NOTHING  exactly k shards present: nothing could be checked
+ *   bit 28     HBEC_COR_LEFT     at least one inconsistent byte position was left as it is
+ *   bits 0..15 corrected         bit j: present shard j had at least one byte corrected
+ * An entry is fully corrected when HBEC_COR_BAD is set and HBEC_COR_LEFT is clear.
+ * Per byte position x, with survivors, checked shards, rows and the syndrome s[0..r) of
+ * hbec_locate_plan_mixed: s == 0: nothing.  r = 1: left as it is.  r >= 2 and exactly one
+ * non-zero component, at q: checked shard q is the candidate, e = s[q].  r >= 2, all r
+ * non-zero and s[q] rows[0][t] == s[0] rows[q][t] for every q: survivor t is the candidate,
+ * e = s[0] / rows[0][t].  A candidate: shard[x] ^= e, that one byte and nothing else; the
+ * position is consistent afterwards.  No candidate: left as it is.  Missing shards are never
+ * written: hbec_repair_plan_mixed after this call rebuilds them from the corrected survivors
+ * and checks the surplus shards again.  A sweep is hbec_verify_plan_mixed, this call with its
+ * flags, hbec_repair_plan_mixed, hbec_etag_plan_mixed, queued on one stream.
+ * With r >= 3 a position with two bad bytes never has a candidate and is never touched.
+ * With r = 2 the code has distance 3: two bad bytes at one position can imitate a third
+ * shard (hbec_locate_plan_mixed's caveat), and that position is then made consistent but
+ * wrong; the object's ETag at the end of the sweep is what catches it.
+ * k <= 12 with m <= 4 and shards below 2^31 - 64 KiB take one launch (per 2^31 - 1 tiles)
+ * whatever the number of stripes, patterns or bad bytes.  Every other non-empty entry gets
+ * HBEC_COR_SKIPPED, filtered or not, and is counted: there is no per-stripe fallback.
+ * d_fixed may be NULL only for a plan built from no entries.  Queued on hip_stream and not
+ * waited for; calls on one plan take turns with the other _mixed calls. */
+#define HBEC_COR_BAD 0x80000000u
+#define HBEC_COR_SKIPPED 0x40000000u
+#define HBEC_COR_NOTHING 0x20000000u
+#define HBEC_COR_LEFT 0x10000000u
+int hbec_correct_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                            const uint32_t* pattern_of, const uint32_t* d_flags /* may be NULL */,
+                            uint32_t* d_fixed, void* hip_stream);
+/* launches since load of the correct kernel, and entries given HBEC_COR_SKIPPED */
+int hbec_correct_plan_stats(uint64_t* kernel_launches, uint64_t* skipped_entries);
+/* shard bytes per wave tile of the correct kernel */
+int hbec_correct_plan_tile_bytes(void);
+/* test hook, as hbec_set_verify_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
+int hbec_set_correct_plan_chunk_tiles(uint64_t tiles);
 /* hbec_verify_plan_mixed and hbec_reconstruct_plan_mixed in one pass over the plan: every
  * stripe's missing shards are rebuilt and its surplus present shards are checked while its k
  * survivors are read once ((k + checked + rebuilt) S bytes moved per stripe instead of
