@@ -783,6 +783,50 @@ class StripePlan:
             self.enc.handle, self._h, starts.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
             ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), d, _stream_ptr(stream)))
 
+    def split_select(self, srcs, lens, select, stream=None):
+        """split with ecSplit's writers (hbec_split_plan_select): ``select`` is
+        an [n, k+m] uint8 array, and shard j of entry i is written whole if and
+        only if select[i][j] is set; a parity shard is coded only if selected
+        and nothing else is written.  A row of zeros skips the entry, as
+        lens[i] = 0 does.  With no parity selected only the selected data
+        shards' pieces are read.  The source may lie over unselected shards:
+        with srcs[i] the entry's data region and parity alone selected this
+        is an in-place encode of the chosen rows.  Queued on the stream."""
+        import numpy as np
+
+        patterns, pattern_of = self._patterns(select)
+        if len(srcs) != self._n or len(lens) != self._n:
+            raise ValueError("srcs and lens need one element per entry")
+        d = (C.c_void_p * max(1, self._n))(*[int(a) for a in srcs])
+        ln = np.zeros(max(1, self._n), np.uint64)
+        ln[:self._n] = [int(x) for x in lens]
+        check(N.lib().hbec_split_plan_select(
+            self.enc.handle, self._h, d, ln.ctypes.data_as(C.POINTER(C.c_uint64)), patterns.ctypes.data_as(N._U8P),
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), patterns.shape[0], _stream_ptr(stream)))
+
+    def split_files_select(self, srcs, select, stream=None):
+        """split_select for a ``files=`` plan, object by object
+        (hbec_split_plan_files_select): object g, its content length in bytes
+        at the device address srcs[g], is written into its selected shard
+        files.  ``select`` stays per ENTRY ([object_start[-1], k+m]): a writer
+        may fail between two stripes."""
+        import numpy as np
+
+        if getattr(self, "_content_lengths", None) is None:
+            raise ValueError("split_files_select needs a plan built from files=")
+        patterns, pattern_of = self._patterns(select)
+        n_obj = len(self._content_lengths)
+        if len(srcs) != n_obj:
+            raise ValueError("srcs needs one address per object")
+        d = (C.c_void_p * max(1, n_obj))(*[int(a) for a in srcs])
+        ln = np.zeros(max(1, n_obj), np.uint64)
+        ln[:n_obj] = self._content_lengths
+        starts = np.ascontiguousarray(self.object_start, dtype=np.uint32)
+        check(N.lib().hbec_split_plan_files_select(
+            self.enc.handle, self._h, starts.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
+            ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), d, patterns.ctypes.data_as(N._U8P),
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), patterns.shape[0], _stream_ptr(stream)))
+
 
 def glue_plan_stats():
     """Since load, for StripePlan.glue_mixed / glue_files: launches of the glue
@@ -850,6 +894,15 @@ def split_plan_tile_bytes() -> int:
 def set_split_plan_chunk_tiles(tiles: int) -> None:
     """Test hook: split kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_split_plan_chunk_tiles(int(tiles)))
+
+
+def split_select_stats():
+    """Since load, for StripePlan.split_select / split_files_select: launches of
+    the select kernel (`kernel_launches`) and, on the per-entry route,
+    device-to-device copies, memsets and applies (`per_stripe_calls`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_split_select_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "per_stripe_calls": b.value}
 
 
 def hash_files_stats():

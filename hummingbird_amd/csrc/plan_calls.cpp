@@ -19,9 +19,11 @@
 // records and list and stage a destination per entry beside the words.  The
 // inverse, every entry's shards from its object bytes (hbec_split_plan and
 // hbec_split_plan_files; splitplan.h, splitplan.hip), walks them too and stages
-// a source per entry.  Any byte range of every entry (hbec_glue_plan_range and
-// hbec_glue_plan_files_range; gluerange.h, gluerange.hip) is the glue call with a
-// start beside each length.  The ETag of every object (hbec_etag_plan_mixed and
+// a source per entry; with a writers mask per entry (hbec_split_plan_select and
+// hbec_split_plan_files_select; splitselect.h, splitselect.hip) it writes the
+// chosen shards alone.  Any byte range of every entry (hbec_glue_plan_range and
+// hbec_glue_plan_files_range; gluerange.h, gluerange.hip) is the glue call with
+// a start beside each length.  The ETag of every object (hbec_etag_plan_mixed and
 // hbec_etag_plan_files; etag.h, etag.hip) decodes what is missing through that
 // call into scratch and hashes the object bytes where they lie, on the hash
 // calls' records.
@@ -54,6 +56,7 @@
 #include "repair.h"
 #include "shardplan.h"
 #include "splitplan.h"
+#include "splitselect.h"
 #include "vmixed.h"
 
 using hbec::current_cus;
@@ -66,7 +69,7 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
     std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal, correct); chains (hash calls)
@@ -173,10 +176,11 @@ int staged_launches(const hbec_plan* plan, const std::vector<uint32_t>& stage, h
 
 // The launches of a kernel that walks the plan's {entry, tile} list: one per
 // chunk of n_tiles tiles (all of them in one, unless the call's test hook says
-// otherwise), counted, until one fails.  launch(t0, nt) -> hipError_t.
+// otherwise), counted, until one fails.  launch(t0, nt) -> hipError_t.  hook_of:
+// the call whose test hook bounds the launches, where it is another's.
 template <class Launch>
-Queued walk_chunks(Call c, uint64_t n_tiles, const char* what, Launch&& launch) {
-    const uint64_t hook = g_calls[c].chunk_tiles.load(std::memory_order_relaxed);
+Queued walk_chunks(Call c, uint64_t n_tiles, const char* what, Launch&& launch, Call hook_of = kCalls) {
+    const uint64_t hook = g_calls[hook_of == kCalls ? c : hook_of].chunk_tiles.load(std::memory_order_relaxed);
     const uint64_t chunk = std::min<uint64_t>((1ull << 31) - 1, hook ? hook : ~0ull);
     hipError_t e = hipSuccess;
     for (uint64_t t0 = 0; t0 < n_tiles && e == hipSuccess; t0 += chunk) {
@@ -1532,6 +1536,210 @@ int split_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* o
     return split_plan(codec, plan, srcs.data(), lens.data(), stream);
 }
 
+// ---- chosen shards of every entry from its object bytes (hbec_split_plan_select) ----
+
+// The other route (any k, m, S), one source entry with something selected: what
+// split_other_entry does, for the selected shards alone.  A selected data shard is a clipped copy and
+// a memset where the pad reaches it.  With a parity row selected, one apply of
+// the selected rows reads whole data shards: from the source where the shard is
+// all piece, from the shard just written where it is selected, and from scratch
+// (copy and memset again) where the pad reaches an unselected one.
+int split_select_other_entry(const hbec_plan* plan, uint32_t i, const uint8_t* mask, const std::vector<uint8_t>& rows,
+                             uint64_t src, uint64_t len, hipStream_t stream) {
+    const int k = plan->k, m = plan->m;
+    const uint64_t S = plan->src[i].shard_len;
+    auto cut = [&](int j, uint8_t* dst) -> int {
+        const uint64_t V = hbec::split_valid(len, (uint64_t)j, S);
+        if (V) {
+            count(g_calls[kSplitSelect].second);
+            const hipError_t e = hipMemcpyAsync(dst, reinterpret_cast<const void*>(src + (uint64_t)j * S), V,
+                                                hipMemcpyDeviceToDevice, stream);
+            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync (split select)");
+        }
+        if (V < S) {
+            count(g_calls[kSplitSelect].second);
+            const hipError_t e = hipMemsetAsync(dst + V, 0, S - V, stream);
+            if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync (split select)");
+        }
+        return HBEC_OK;
+    };
+    size_t n_staged = 0;
+    for (int j = 0; j < k; ++j) {
+        if (mask[j]) {
+            const int rc = cut(j, reinterpret_cast<uint8_t*>(shard_addr(plan, i, j)));
+            if (rc) return rc;
+        } else if (hbec::split_valid(len, (uint64_t)j, S) < S) {
+            ++n_staged;
+        }
+    }
+    const int R = hbec::ss_parity_count(k, m, mask);
+    if (R == 0) return HBEC_OK;
+    void* scratch = nullptr;
+    if (n_staged) {
+        const int rc = hbec::scratch_alloc(n_staged * (size_t)S, stream, &scratch);
+        if (rc) return rc;
+    }
+    uint8_t* slot = static_cast<uint8_t*>(scratch);
+    std::vector<hbec_view> vin((size_t)k), vout((size_t)R);
+    std::vector<uint8_t> sel((size_t)R * k);
+    int rc = HBEC_OK;
+    for (int j = 0; j < k && !rc; ++j) {
+        if (hbec::split_valid(len, (uint64_t)j, S) == S) {
+            vin[j] = hbec_view{reinterpret_cast<void*>(src + (uint64_t)j * S), 0};
+        } else if (mask[j]) {
+            vin[j] = hbec_view{reinterpret_cast<void*>(shard_addr(plan, i, j)), 0};
+        } else {
+            rc = cut(j, slot);
+            vin[j] = hbec_view{slot, 0};
+            slot += S;
+        }
+    }
+    for (int r = 0, q = 0; r < m; ++r) {
+        if (!mask[k + r]) continue;
+        std::memcpy(sel.data() + (size_t)q * k, rows.data() + (size_t)r * k, (size_t)k);
+        vout[q++] = hbec_view{reinterpret_cast<void*>(shard_addr(plan, i, k + r)), 0};
+    }
+    if (!rc) {
+        count(g_calls[kSplitSelect].second);
+        rc = hbec::apply_views(R, k, sel.data(), vin.data(), vout.data(), 1, S, stream);
+    }
+    if (scratch) hbec::scratch_free(scratch, stream);
+    return rc;
+}
+
+int split_plan_select(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
+                      const uint8_t* patterns, const uint32_t* pattern_of, uint32_t n_patterns, hipStream_t stream) {
+    if (!codec || !plan || !srcs || !src_lens || !patterns || !pattern_of)
+        return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
+    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
+    if (n_patterns > 65536) return fail(HBEC_ERR_INVALID_ARG, "more than 65536 patterns");
+    const uint64_t n_src = plan->n_src;
+    if (n_src && !n_patterns) return fail(HBEC_ERR_INVALID_ARG, "stripes but no patterns");
+    for (uint64_t i = 0; i < n_src; ++i)  // zero-length entries too
+        if (pattern_of[i] >= n_patterns)
+            return fail(HBEC_ERR_INVALID_ARG, "pattern index out of range (stripe " + std::to_string(i) + ")");
+    std::vector<uint8_t> selected(n_patterns, 0);  // the mask has a byte set
+    for (uint32_t p = 0; p < n_patterns; ++p)
+        for (int sh = 0; sh < n; ++sh) selected[p] |= patterns[(size_t)p * n + sh] ? 1 : 0;
+    // an entry has work where it is given bytes and a shard of it is selected
+    auto has_work = [&](uint64_t i) { return src_lens[i] != 0 && selected[pattern_of[i]]; };
+    bool any = false;
+    for (uint64_t i = 0; i < n_src; ++i) {
+        const uint64_t S = plan->src[i].shard_len, len = src_lens[i];
+        const uint64_t src = reinterpret_cast<uintptr_t>(srcs[i]);
+        if (!len) continue;
+        if (!hbec::split_len_ok(len, (uint64_t)k, S))
+            return fail(HBEC_ERR_INVALID_ARG,
+                        "src_lens does not give the entry's shard length (entry " + std::to_string(i) + ")");
+        if (!has_work(i)) continue;  // nothing selected: the source is not looked at
+        if (!src) return fail(HBEC_ERR_INVALID_ARG, "null source with src_lens > 0 (entry " + std::to_string(i) + ")");
+        const uint8_t* mask = patterns + (size_t)pattern_of[i] * n;
+        for (int sh = 0; sh < n; ++sh)  // an unselected shard is not written: the source may lie over it
+            if (mask[sh] && hbec::glue_overlaps(src, len, shard_addr(plan, (uint32_t)i, sh), S))
+                return fail(HBEC_ERR_INVALID_ARG, "source overlaps selected shard " + std::to_string(sh) +
+                                                      " of its own entry (entry " + std::to_string(i) + ")");
+        any = true;
+    }
+    if (!any) return HBEC_OK;  // nothing given or nothing selected
+    // the records and the list are the split call's (a plan of m = 0 has its own, plan_internal.h)
+    const bool own = m == 0;
+    int rc = own ? walk_list_device(plan, 1, &plan->sp_built, &plan->d_sprecs, &plan->d_sptiles, &plan->n_sptiles,
+                                    &plan->sp_other)
+                 : mixed_plan_device(plan);
+    if (rc) return rc;
+    const hbec::MRec* d_recs = own ? plan->d_sprecs : plan->d_mrecs;
+    const hbec::MTile* d_tiles = own ? plan->d_sptiles : plan->d_mtiles;
+    const uint64_t n_tiles = own ? plan->n_sptiles : plan->n_mtiles;
+    const std::vector<uint32_t>& other = own ? plan->sp_other : plan->mp_other;
+    // the encode rows: rows k..k+m-1 of the coding matrix
+    std::vector<uint8_t> mat((size_t)n * k);
+    hbec_matrix(codec, mat.data());
+    const std::vector<uint8_t> rows(mat.begin() + (size_t)k * k, mat.end());
+
+    if (n_tiles > 0) {
+        // One record per distinct mask the kernel's entries use, one word per
+        // source entry and its piece; one launch per chunk of the list, of the
+        // instance for the largest count of selected parity rows in use.
+        auto mine = [&](uint64_t i) {  // mp_build's route
+            return has_work(i) && plan->src[i].shard_len != 0 && hbec::pos32_shard(plan->src[i].shard_len);
+        };
+        std::vector<uint8_t> used(n_patterns, 0);
+        for (uint64_t i = 0; i < n_src; ++i)
+            if (mine(i)) used[pattern_of[i]] = 1;
+        std::vector<uint32_t> stage, word_of(n_patterns, hbec::kSsSkip);
+        int rmax = 0;
+        bool work = false;
+        for (uint32_t p = 0; p < n_patterns; ++p) {
+            if (!used[p]) continue;
+            int R = 0;
+            const uint32_t rec = hbec::ss_record(stage, k, m, patterns + (size_t)p * n, rows.data(), &R);
+            word_of[p] = ((uint32_t)R << hbec::kSsShift) | rec;
+            rmax = std::max(rmax, R);
+            work = true;
+        }
+        if (work) {
+            const size_t rec_words = stage.size();
+            stage.resize(rec_words + 5 * (size_t)n_src);
+            const size_t src_at = rec_words + (size_t)n_src;
+            for (uint64_t i = 0; i < n_src; ++i) {
+                const uint64_t src = reinterpret_cast<uintptr_t>(srcs[i]), len = src_lens[i];
+                stage[rec_words + i] = mine(i) ? word_of[pattern_of[i]] : hbec::kSsSkip;
+                uint32_t* d = stage.data() + src_at + 4 * i;
+                d[0] = (uint32_t)src, d[1] = (uint32_t)(src >> 32), d[2] = (uint32_t)len, d[3] = (uint32_t)(len >> 32);
+            }
+            int cus = 0;
+            rc = current_cus(&cus);
+            if (rc) return rc;
+            rc = staged_launches(plan, stage, stream, [&](const uint32_t* d_pats) {
+                return walk_chunks(
+                    kSplitSelect, n_tiles, "launch gf_split_select_plan",
+                    [&](uint64_t t0, uint32_t nt) {
+                        return (hipError_t)hbec::launch_split_select_plan(k, rmax, d_recs, d_tiles + t0, nt,
+                                                                          d_pats + rec_words, d_pats + src_at, d_pats,
+                                                                          cus, stream, plan->shards);
+                    },
+                    kSplit);  // hbec_set_split_plan_chunk_tiles bounds these launches too
+            });
+            if (rc) return rc;
+        }
+    }
+    // the other route, one entry at a time (any k, m, S)
+    for (uint32_t i : other) {
+        if (!has_work(i)) continue;
+        rc = split_select_other_entry(plan, i, patterns + (size_t)pattern_of[i] * n, rows,
+                                      reinterpret_cast<uintptr_t>(srcs[i]), src_lens[i], stream);
+        if (rc) return rc;
+    }
+    return HBEC_OK;
+}
+
+// ---- whole objects of a files plan into chosen shard files (hbec_split_plan_files_select) ----
+
+int split_plan_files_select(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                            uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                            const void* const* object_srcs, const uint8_t* patterns, const uint32_t* pattern_of,
+                            uint32_t n_patterns, hipStream_t stream) {
+    if (!codec || !plan || !content_lengths || !object_srcs || !patterns || !pattern_of)
+        return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
+    if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
+    const uint64_t n_src = plan->n_src;
+    std::vector<const void*> srcs((size_t)std::max<uint64_t>(1, n_src), nullptr);
+    std::vector<uint64_t> lens((size_t)std::max<uint64_t>(1, n_src), 0u);
+    if (n_src) {
+        const int rc = files_cut_entries(plan, object_start, n_objects, content_lengths, chunk_size,
+                                         [&](uint32_t g, uint64_t i, uint64_t off, uint64_t len) {
+                                             lens[i] = len;
+                                             srcs[i] = object_srcs[g]
+                                                           ? static_cast<const uint8_t*>(object_srcs[g]) + off
+                                                           : nullptr;
+                                         });
+        if (rc) return rc;
+    }
+    return split_plan_select(codec, plan, srcs.data(), lens.data(), patterns, pattern_of, n_patterns, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1797,6 +2005,29 @@ int hbec_split_plan_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
 
 int hbec_set_split_plan_chunk_tiles(uint64_t tiles) {
     return set_chunk_tiles("hbec_set_split_plan_chunk_tiles", kSplit, tiles);
+}
+
+int hbec_split_plan_select(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
+                           const uint8_t* patterns, const uint32_t* pattern_of, uint32_t n_patterns,
+                           void* hip_stream) {
+    return hbec::guarded("hbec_split_plan_select", [&]() -> int {
+        return split_plan_select(codec, plan, srcs, src_lens, patterns, pattern_of, n_patterns,
+                                 static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_split_plan_files_select(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                                 uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                                 const void* const* object_srcs, const uint8_t* patterns, const uint32_t* pattern_of,
+                                 uint32_t n_patterns, void* hip_stream) {
+    return hbec::guarded("hbec_split_plan_files_select", [&]() -> int {
+        return split_plan_files_select(codec, plan, object_start, n_objects, content_lengths, chunk_size, object_srcs,
+                                       patterns, pattern_of, n_patterns, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_split_select_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
+    return call_stats("hbec_split_select_stats", kSplitSelect, kernel_launches, per_stripe_calls);
 }
 
 }  // extern "C"

@@ -917,7 +917,7 @@ int hbec_etag_plan_stats(uint64_t* kernel_launches, uint64_t* chains, uint64_t* 
  * k+m shards of the entry are written whole, [0, S_i) each, and nothing else; the source is
  * read once and not modified, and no 16-byte block without a byte of O_i is read.
  * src_lens[i] = 0 skips the entry.  The call takes no mask: a writers mask (ecSplit's nil
- * writers) is not offered.
+ * writers) is hbec_split_plan_select's.
  * Errors, all HBEC_ERR_INVALID_ARG and all found before anything is queued, in this order:
  * a null codec, plan, srcs or src_lens; a plan built for another (k, m); then per entry
  * with src_lens[i] > 0, named by entry: a length whose ecShardLength, ceil(src_lens[i] / k),
@@ -951,6 +951,54 @@ int hbec_split_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls)
 int hbec_split_plan_tile_bytes(void);
 /* test hook of the ecutils.go:26-72 batch call, as hbec_set_mixed_plan_chunk_tiles */
 int hbec_set_split_plan_chunk_tiles(uint64_t tiles);
+
+/* ecSplit (ecutils.go:26-72) with its writers, for every entry of a plan in one call.
+ * ecSplit writes shard i of a stripe only where writers[i] != nil && !failed[i] (line 63):
+ * a stabilize retried after some nodes stored their shard, a node that needs one shard of
+ * an object it holds whole, a re-stabilize of one ring position.  It is hbec_split_plan
+ * with a mask per entry.  Masks travel as the _mixed calls' do: patterns holds the
+ * distinct rows, n_patterns of k+m bytes each, and pattern_of one row index per source
+ * entry (zero-length entries included); both are host arrays, copied before the call
+ * returns.  Entry i is cut and zero-padded exactly as hbec_split_plan cuts and pads it.
+ * Shard j of it is written whole, [0, S_i), if and only if byte j of its row is not 0; a
+ * parity shard is coded only if selected; no byte of an unselected shard and no byte
+ * outside the selected shards is written.  With every byte set the bytes written are
+ * hbec_split_plan's.  A row of zeros, or src_lens[i] = 0, skips the entry before any load.
+ * With no parity selected only the pieces of the selected data shards are read; with one
+ * selected, every data shard with a byte of O_i is read once.  The source may touch, but
+ * not overlap, the entry's selected shards; it may overlap unselected ones, which are only
+ * read as part of the source: with srcs[i] the entry's own data region and parity alone
+ * selected the call is an in-place encode of the chosen rows.
+ * Errors, all HBEC_ERR_INVALID_ARG and all found before anything is queued, in this order:
+ * a null codec, plan, srcs, src_lens, patterns or pattern_of; a plan built for another
+ * (k, m); more than 65536 patterns; n_patterns = 0 for a plan with entries; a pattern_of[i]
+ * >= n_patterns (any entry); then per entry with src_lens[i] > 0, named by entry: a length
+ * whose ecShardLength is not S_i, and, where a shard of it is selected, a null srcs[i] and a
+ * source range that overlaps one of the entry's selected shards.
+ * The work is queued on hip_stream and not waited for.  k <= 12 with m <= 4 (m = 0
+ * included) runs as one launch whatever the entries, lengths or masks (and per
+ * hbec_set_split_plan_chunk_tiles tiles under that hook); a call with nothing to write
+ * launches nothing.  Other shapes, and shards of 2^31 - 64 KiB bytes or more, go per entry:
+ * per selected data shard a clipped copy and a memset where the pad reaches it; with a
+ * parity shard selected, the same into scratch for each unselected data shard the pad
+ * reaches, and one apply of the selected rows.  Calls on one plan take turns with the
+ * _mixed calls. */
+int hbec_split_plan_select(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs,
+                           const uint64_t* src_lens, const uint8_t* patterns, const uint32_t* pattern_of,
+                           uint32_t n_patterns, void* hip_stream);
+/* ecSplit with its writers (ecutils.go:26-72, line 63) for a batch, on hbec_plan_files
+ * plans: hbec_split_plan_files with a mask per ENTRY, since a writer can fail between two
+ * stripes.  Sources and lengths are per object as there; patterns / pattern_of as in
+ * hbec_split_plan_select.  Errors: a null codec, plan, content_lengths, object_srcs,
+ * patterns or pattern_of; another (k, m); what hbec_split_plan_files says of object_start,
+ * chunk_size and the content lengths; then hbec_split_plan_select's. */
+int hbec_split_plan_files_select(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                                 uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                                 const void* const* object_srcs, const uint8_t* patterns,
+                                 const uint32_t* pattern_of, uint32_t n_patterns, void* hip_stream);
+/* ecSplit with its writers (ecutils.go:26-72, line 63) batch call: launches since load of
+ * the select kernel, and copies, memsets and applies of the per-entry route */
+int hbec_split_select_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
 
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
