@@ -617,6 +617,61 @@ class StripePlan:
             ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), patterns.ctypes.data_as(N._U8P),
             patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, _stream_ptr(stream)))
 
+    def _fixed_ptr(self, fixed):
+        import torch
+
+        if fixed.dtype != torch.uint32 and fixed.dtype != torch.int32:
+            raise ValueError("fixed must be a 32-bit integer tensor")
+        if not fixed.is_cuda or not fixed.is_contiguous() or fixed.numel() < self._n:
+            raise ValueError("fixed must be a contiguous CUDA tensor with one entry per stripe")
+        return C.c_void_p(fixed.data_ptr())
+
+    def glue_checked(self, present, dsts, lens, fixed, stream=None):
+        """glue_mixed that reads every PRESENT shard once, checks the surplus
+        ones and writes the object bytes of the corrected codeword
+        (hbec_glue_plan_checked): read-repair on GET.  No shard is written.
+        Shard positions below min(S_i, lens[i]) are examined by correct_mixed's
+        rule; a bad byte of a data shard is written corrected, a missing data
+        shard is decoded from the corrected survivors.  ``fixed`` as in
+        correct_mixed (caller-zeroed, ORed into): COR_BAD, COR_LEFT,
+        COR_NOTHING (exactly k present: glued as glue_mixed does), COR_SKIPPED
+        (the other route: glued, not checked) and, in bits 0..15, the shards a
+        byte was taken as corrected in.  lens[i] = 0 skips the entry and its word."""
+        import numpy as np
+
+        patterns, pattern_of = self._patterns(present)
+        if len(dsts) != self._n or len(lens) != self._n:
+            raise ValueError("dsts and lens need one element per entry")
+        d = (C.c_void_p * max(1, self._n))(*[int(a) for a in dsts])
+        ln = np.zeros(max(1, self._n), np.uint64)
+        ln[:self._n] = [int(x) for x in lens]
+        check(N.lib().hbec_glue_plan_checked(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, ln.ctypes.data_as(C.POINTER(C.c_uint64)),
+            self._fixed_ptr(fixed), _stream_ptr(stream)))
+
+    def glue_files_checked(self, present, outs, fixed, stream=None):
+        """glue_checked for a ``files=`` plan, object by object
+        (hbec_glue_plan_files_checked): objects are cut as glue_files cuts them;
+        ``present`` and ``fixed`` stay per ENTRY."""
+        import numpy as np
+
+        if getattr(self, "_content_lengths", None) is None:
+            raise ValueError("glue_files_checked needs a plan built from files=")
+        patterns, pattern_of = self._patterns(present)
+        n_obj = len(self._content_lengths)
+        if len(outs) != n_obj:
+            raise ValueError("outs needs one address per object")
+        d = (C.c_void_p * max(1, n_obj))(*[int(a) for a in outs])
+        ln = np.zeros(max(1, n_obj), np.uint64)
+        ln[:n_obj] = self._content_lengths
+        starts = np.ascontiguousarray(self.object_start, dtype=np.uint32)
+        check(N.lib().hbec_glue_plan_files_checked(
+            self.enc.handle, self._h, starts.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
+            ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), patterns.ctypes.data_as(N._U8P),
+            patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, self._fixed_ptr(fixed),
+            _stream_ptr(stream)))
+
     def glue_range(self, present, dsts, starts, lens, stream=None):
         """Any byte range of every entry in one call (hbec_glue_plan_range): with
         D_i entry i's data shards 0..k-1 back to back as in glue_mixed, the
@@ -845,6 +900,25 @@ def glue_plan_tile_bytes() -> int:
 def set_glue_plan_chunk_tiles(tiles: int) -> None:
     """Test hook: glue kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_glue_plan_chunk_tiles(int(tiles)))
+
+
+def glue_checked_stats():
+    """Since load, for StripePlan.glue_checked / glue_files_checked: launches of
+    the checked glue kernel (`kernel_launches`) and, on the per-entry route
+    (glued, not checked), copies and applies (`per_stripe_calls`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_glue_checked_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "per_stripe_calls": b.value}
+
+
+def glue_checked_tile_bytes() -> int:
+    """Shard bytes per wave tile of the checked glue kernel."""
+    return int(N.lib().hbec_glue_checked_tile_bytes())
+
+
+def set_glue_checked_chunk_tiles(tiles: int) -> None:
+    """Test hook: checked glue kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_glue_checked_chunk_tiles(int(tiles)))
 
 
 def glue_range_stats():

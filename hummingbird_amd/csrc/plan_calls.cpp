@@ -23,7 +23,10 @@
 // hbec_split_plan_files_select; splitselect.h, splitselect.hip) it writes the
 // chosen shards alone.  Any byte range of every entry (hbec_glue_plan_range and
 // hbec_glue_plan_files_range; gluerange.h, gluerange.hip) is the glue call with
-// a start beside each length.  The ETag of every object (hbec_etag_plan_mixed and
+// a start beside each length.  The glue that reads every present shard, checks the
+// surplus ones and corrects what it writes (hbec_glue_plan_checked and
+// hbec_glue_plan_files_checked; gluecheck.h, gluecheck.hip) stages glue's
+// destinations beside records of its own.  The ETag of every object (hbec_etag_plan_mixed and
 // hbec_etag_plan_files; etag.h, etag.hip) decodes what is missing through that
 // call into scratch and hashes the object bytes where they lie, on the hash
 // calls' records.
@@ -44,6 +47,7 @@
 #include "etag.h"
 #include "gf256.h"
 #include "glue.h"
+#include "gluecheck.h"
 #include "gluerange.h"
 #include "hashfiles.h"
 #include "hashplan.h"
@@ -69,7 +73,7 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kGlueChecked, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
     std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal, correct); chains (hash calls)
@@ -896,13 +900,13 @@ int hash_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* ob
 // byte wanted are rebuilt by one single-pattern apply, straight into the
 // destination where the shard is written whole, through scratch and a clipped
 // copy where it is cut (at most one shard of an entry is).  Every copy and every
-// apply counts as a per-stripe call.
+// apply counts as a per-stripe call, of the call `c`.
 int glue_other_entry(const hbec_plan* plan, uint32_t i, const uint8_t* mask, const ShardSet& out, uint64_t dst,
-                     uint64_t len, hipStream_t stream) {
+                     uint64_t len, hipStream_t stream, Call c = kGlue) {
     const int k = plan->k;
     const uint64_t S = plan->src[i].shard_len;
     auto copy = [&](uint64_t to, const void* from, uint64_t bytes) -> int {
-        count(g_calls[kGlue].second);
+        count(g_calls[c].second);
         const hipError_t e = hipMemcpyAsync(reinterpret_cast<void*>(to), from, bytes, hipMemcpyDeviceToDevice, stream);
         return e == hipSuccess ? HBEC_OK : hip_fail(e, "hipMemcpyAsync (glue)");
     };
@@ -934,7 +938,7 @@ int glue_other_entry(const hbec_plan* plan, uint32_t i, const uint8_t* mask, con
         vout[s] = hbec_view{q == cut ? scratch : reinterpret_cast<void*>(dst + (uint64_t)out.idx[q] * S), 0};
         std::memcpy(rows.data() + s * (size_t)k, out.rows.data() + q * (size_t)k, (size_t)k);
     }
-    count(g_calls[kGlue].second);
+    count(g_calls[c].second);
     int rc = hbec::apply_views((int)sel.size(), k, rows.data(), vin.data(), vout.data(), 1, S, stream);
     if (!rc && scratch)
         rc = copy(dst + (uint64_t)out.idx[cut] * S, scratch, hbec::glue_valid(len, (uint64_t)out.idx[cut], S));
@@ -942,16 +946,13 @@ int glue_other_entry(const hbec_plan* plan, uint32_t i, const uint8_t* mask, con
     return rc;
 }
 
-int glue_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                    const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens, hipStream_t stream) {
-    std::vector<PlanPattern> pats;
-    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
-    if (rc) return rc;
+// What hbec_glue_plan_mixed checks of its destinations, after the patterns'
+// checks; hbec_glue_plan_checked makes the same.  *any: some entry has bytes asked for.
+int check_glue_dsts(const hbec_plan* plan, void* const* dsts, const uint64_t* dst_lens, bool* any) {
     if (!dsts || !dst_lens) return fail(HBEC_ERR_INVALID_ARG, "null argument");
     const int k = plan->k, n = k + plan->m;
-    const uint64_t n_src = plan->n_src;
-    bool any = false;
-    for (uint64_t i = 0; i < n_src; ++i) {  // zero-length entries too
+    *any = false;
+    for (uint64_t i = 0; i < plan->n_src; ++i) {  // zero-length entries too
         const uint64_t S = plan->src[i].shard_len, len = dst_lens[i];
         const uint64_t dst = reinterpret_cast<uintptr_t>(dsts[i]);
         if ((unsigned __int128)len > (unsigned __int128)S * (uint64_t)k)
@@ -962,9 +963,33 @@ int glue_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* pat
             if (hbec::glue_overlaps(dst, len, shard_addr(plan, (uint32_t)i, sh), S))
                 return fail(HBEC_ERR_INVALID_ARG, "destination overlaps shard " + std::to_string(sh) +
                                                       " of its own entry (entry " + std::to_string(i) + ")");
-        any = true;
+        *any = true;
     }
+    return HBEC_OK;
+}
+
+// {address lo, hi, length lo, hi} per source entry, appended to a call's staging words
+size_t stage_glue_dsts(const hbec_plan* plan, void* const* dsts, const uint64_t* dst_lens, std::vector<uint32_t>& stage) {
+    const size_t dst_at = stage.size();
+    stage.resize(dst_at + 4 * (size_t)plan->n_src);
+    for (uint64_t i = 0; i < plan->n_src; ++i) {
+        const uint64_t dst = reinterpret_cast<uintptr_t>(dsts[i]), len = dst_lens[i];
+        uint32_t* d = stage.data() + dst_at + 4 * i;
+        d[0] = (uint32_t)dst, d[1] = (uint32_t)(dst >> 32), d[2] = (uint32_t)len, d[3] = (uint32_t)(len >> 32);
+    }
+    return dst_at;
+}
+
+int glue_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                    const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens, hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    bool any = false;
+    rc = check_glue_dsts(plan, dsts, dst_lens, &any);
+    if (rc) return rc;
     if (!any) return HBEC_OK;  // nothing asked for
+    const int k = plan->k, n = k + plan->m;
     bool used = false;
     rc = resolve_patterns(codec, patterns, true, true, false, pats, &used);
     if (rc) return rc;
@@ -996,13 +1021,7 @@ int glue_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* pat
                 rmax = std::max(rmax, r);
                 return ((uint32_t)r << hbec::kMPatShift) | pp.rec;
             });
-        const size_t dst_at = stage.size();
-        stage.resize(dst_at + 4 * (size_t)n_src);
-        for (uint64_t i = 0; i < n_src; ++i) {
-            const uint64_t dst = reinterpret_cast<uintptr_t>(dsts[i]), len = dst_lens[i];
-            uint32_t* d = stage.data() + dst_at + 4 * i;
-            d[0] = (uint32_t)dst, d[1] = (uint32_t)(dst >> 32), d[2] = (uint32_t)len, d[3] = (uint32_t)(len >> 32);
-        }
+        const size_t dst_at = stage_glue_dsts(plan, dsts, dst_lens, stage);
         if (rmax >= 0) {
             int cus = 0;
             rc = current_cus(&cus);
@@ -1058,25 +1077,120 @@ int files_cut_entries(const hbec_plan* plan, const uint32_t* object_start, uint3
     return HBEC_OK;
 }
 
-int glue_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
-                    const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
-                    uint32_t n_patterns, const uint32_t* pattern_of, void* const* object_dsts, hipStream_t stream) {
+// hbec_glue_plan_files' checks of its own and the cut of every object into its
+// entries' destinations; hbec_glue_plan_files_checked makes the same.
+int glue_files_dsts(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                    const uint64_t* content_lengths, uint64_t chunk_size, void* const* object_dsts,
+                    std::vector<void*>& dsts, std::vector<uint64_t>& lens) {
     if (!codec || !plan || !content_lengths || !object_dsts) return fail(HBEC_ERR_INVALID_ARG, "null argument");
     const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
     if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
     const uint64_t n_src = plan->n_src;
-    std::vector<void*> dsts((size_t)std::max<uint64_t>(1, n_src), nullptr);
-    std::vector<uint64_t> lens((size_t)std::max<uint64_t>(1, n_src), 0u);
-    if (n_src) {
-        const int rc = files_cut_entries(plan, object_start, n_objects, content_lengths, chunk_size,
-                                         [&](uint32_t g, uint64_t i, uint64_t off, uint64_t len) {
-                                             lens[i] = len;
-                                             dsts[i] = object_dsts[g] ? static_cast<uint8_t*>(object_dsts[g]) + off
-                                                                      : nullptr;
-                                         });
-        if (rc) return rc;
-    }
+    dsts.assign((size_t)std::max<uint64_t>(1, n_src), nullptr);
+    lens.assign((size_t)std::max<uint64_t>(1, n_src), 0u);
+    if (!n_src) return HBEC_OK;
+    return files_cut_entries(plan, object_start, n_objects, content_lengths, chunk_size,
+                             [&](uint32_t g, uint64_t i, uint64_t off, uint64_t len) {
+                                 lens[i] = len;
+                                 dsts[i] = object_dsts[g] ? static_cast<uint8_t*>(object_dsts[g]) + off : nullptr;
+                             });
+}
+
+int glue_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                    const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
+                    uint32_t n_patterns, const uint32_t* pattern_of, void* const* object_dsts, hipStream_t stream) {
+    std::vector<void*> dsts;
+    std::vector<uint64_t> lens;
+    const int rc = glue_files_dsts(codec, plan, object_start, n_objects, content_lengths, chunk_size, object_dsts,
+                                   dsts, lens);
+    if (rc) return rc;
     return glue_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), lens.data(), stream);
+}
+
+// ---- the object bytes with the surplus shards checked (hbec_glue_plan_checked) ----
+
+// hbec_glue_plan_mixed that reads every present shard: a record per mask in use
+// with its check rows and its decode rows over the same survivors (gluecheck.h),
+// glue's destinations, and correct's word per entry.  The other route glues as
+// glue_plan_mixed's does, checks nothing and says so.
+int glue_plan_checked(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                      const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens, uint32_t* d_fixed,
+                      hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    bool any = false;
+    rc = check_glue_dsts(plan, dsts, dst_lens, &any);
+    if (rc) return rc;
+    const int k = plan->k, n = k + plan->m;
+    const uint64_t n_src = plan->n_src;
+    if (!d_fixed && n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    for (uint64_t i = 0; i < n_src; ++i)
+        if (hbec::glue_overlaps(reinterpret_cast<uintptr_t>(dsts[i]), dst_lens[i], reinterpret_cast<uintptr_t>(d_fixed),
+                                4 * n_src))
+            return fail(HBEC_ERR_INVALID_ARG, "d_fixed aliases a destination (entry " + std::to_string(i) + ")");
+    if (!any) return HBEC_OK;  // nothing asked for
+    bool used = false;
+    rc = resolve_patterns(codec, patterns, true, true, true, pats, &used);
+    if (rc) return rc;
+    rc = mixed_plan_device(plan);
+    if (rc) return rc;
+
+    if (plan->n_mtiles > 0) {
+        int amax = -1;
+        std::vector<uint32_t> stage;
+        const size_t rec_words = stage_patterns(
+            plan, pats, pattern_of, stage,
+            [&](PlanPattern& pp) {
+                const ShardSet &o = pp.out, &c = pp.chk;
+                pp.rec = hbec::gc_record(stage, k, c.surv.data(), c.idx.data(), (int)c.idx.size(), c.rows.data(),
+                                         o.idx.data(), (int)o.idx.size(), o.rows.data());
+            },
+            [&](uint64_t i, const PlanPattern& pp) {
+                const uint64_t S = plan->src[i].shard_len;
+                if (S == 0 || !hbec::pos32_shard(S) || dst_lens[i] == 0) return hbec::kGlueSkip;  // mp_build's route
+                const int A = (int)(pp.chk.idx.size() + pp.out.idx.size());
+                amax = std::max(amax, A);
+                return hbec::gc_word(A, pp.rec);
+            });
+        const size_t dst_at = stage_glue_dsts(plan, dsts, dst_lens, stage);
+        if (amax >= 0) {
+            int cus = 0;
+            rc = current_cus(&cus);
+            if (rc) return rc;
+            rc = staged_launches(plan, stage, stream, [&](const uint32_t* d_pats) {
+                return walk_chunks(kGlueChecked, plan->n_mtiles, "launch gf_glue_checked",
+                                   [&](uint64_t t0, uint32_t nt) {
+                                       return (hipError_t)hbec::launch_glue_checked(
+                                           k, amax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_pats + rec_words,
+                                           d_pats + dst_at, d_pats, d_fixed, cus, stream, plan->shards);
+                                   });
+            });
+            if (rc) return rc;
+        }
+    }
+    // the other route, one entry at a time (any k, m, S): glued, not checked
+    for (uint32_t i : plan->mp_other) {
+        if (!dst_lens[i]) continue;
+        rc = glue_other_entry(plan, i, patterns + (size_t)pattern_of[i] * n, pats[pattern_of[i]].out,
+                              reinterpret_cast<uintptr_t>(dsts[i]), dst_lens[i], stream, kGlueChecked);
+        if (rc) return rc;
+        const hipError_t e = hbec::launch_vm_or(d_fixed + i, hbec::kCorSkipped, stream);
+        if (e != hipSuccess) return hip_fail(e, "launch gf_vm_or");
+    }
+    return HBEC_OK;
+}
+
+int glue_plan_files_checked(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                            uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                            const uint8_t* patterns, uint32_t n_patterns, const uint32_t* pattern_of,
+                            void* const* object_dsts, uint32_t* d_fixed, hipStream_t stream) {
+    std::vector<void*> dsts;
+    std::vector<uint64_t> lens;
+    const int rc = glue_files_dsts(codec, plan, object_start, n_objects, content_lengths, chunk_size, object_dsts,
+                                   dsts, lens);
+    if (rc) return rc;
+    return glue_plan_checked(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), lens.data(), d_fixed, stream);
 }
 
 // ---- any byte range of every entry from its shards (hbec_glue_plan_range) ----
@@ -1915,6 +2029,36 @@ int hbec_glue_plan_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
 
 int hbec_set_glue_plan_chunk_tiles(uint64_t tiles) {
     return set_chunk_tiles("hbec_set_glue_plan_chunk_tiles", kGlue, tiles);
+}
+
+int hbec_glue_plan_checked(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                           const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens, uint32_t* d_fixed,
+                           void* hip_stream) {
+    return hbec::guarded("hbec_glue_plan_checked", [&]() -> int {
+        return glue_plan_checked(codec, plan, patterns, n_patterns, pattern_of, dsts, dst_lens, d_fixed,
+                                 static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_glue_plan_files_checked(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                                 uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                                 const uint8_t* patterns, uint32_t n_patterns, const uint32_t* pattern_of,
+                                 void* const* object_dsts, uint32_t* d_fixed, void* hip_stream) {
+    return hbec::guarded("hbec_glue_plan_files_checked", [&]() -> int {
+        return glue_plan_files_checked(codec, plan, object_start, n_objects, content_lengths, chunk_size, patterns,
+                                       n_patterns, pattern_of, object_dsts, d_fixed,
+                                       static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_glue_checked_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
+    return call_stats("hbec_glue_checked_stats", kGlueChecked, kernel_launches, per_stripe_calls);
+}
+
+int hbec_glue_checked_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
+
+int hbec_set_glue_checked_chunk_tiles(uint64_t tiles) {
+    return set_chunk_tiles("hbec_set_glue_checked_chunk_tiles", kGlueChecked, tiles);
 }
 
 int hbec_glue_plan_range(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,

@@ -774,6 +774,59 @@ int hbec_glue_plan_tile_bytes(void);
 /* test hook, as hbec_set_mixed_plan_chunk_tiles */
 int hbec_set_glue_plan_chunk_tiles(uint64_t tiles);
 
+/* hbec_glue_plan_mixed with every PRESENT shard read once, the surplus ones checked and the
+ * bytes they prove wrong corrected in what is written: read-repair on GET.  The reference's
+ * GET fetches surplus shards all the time: ecObject.Copy asks for one more shard every 25 ms
+ * (ecobj.go:173-203), and a GET retried after an ETag mismatch (main.go:233-241) fetches
+ * everything.  It is the read-only form of hbec_verify_plan_mixed, hbec_correct_plan_mixed and
+ * hbec_glue_plan_mixed in a row: NO byte of any shard is stored, so the shard buffers may be
+ * a cache shared with other readers.
+ * patterns / n_patterns / pattern_of / dsts / dst_lens: exactly those of hbec_glue_plan_mixed.
+ * Per entry i the survivors are the first k present shards and the checked shards the other
+ * present ones, r of them, as in hbec_check_rows.  The shard positions examined are exactly
+ * x < min(S_i, dst_lens[i]); the rule at each is hbec_correct_plan_mixed's, unchanged.  The
+ * call writes D'_i[0, dst_lens[i]) to dsts[i], where D'_i is hbec_glue_plan_mixed's D_i taken
+ * from the entry as hbec_correct_plan_mixed would leave it over those positions: a present
+ * data shard that is the candidate at x contributes stored ^ e; a missing data shard what
+ * ReconstructData computes from the corrected survivors; a candidate among the checked shards
+ * changes nothing; a position with no candidate (r = 1, or two bad bytes in one column with
+ * r >= 3) contributes what hbec_glue_plan_mixed writes.  Nothing else is stored: no byte
+ * outside [dsts[i], dsts[i] + dst_lens[i]).
+ * d_fixed: uint32, device, one word per source entry, zeroed by the caller, only ever ORed
+ * into; it must not alias a destination.  The bits are hbec_correct_plan_mixed's
+ * (HBEC_COR_BAD, HBEC_COR_LEFT, HBEC_COR_NOTHING: exactly k present, the entry is glued
+ * exactly as hbec_glue_plan_mixed glues it; HBEC_COR_SKIPPED), except that bits 0..15 name
+ * the shards in which a byte was TAKEN AS corrected: the shards themselves are unchanged.
+ * dst_lens[i] = 0 skips the entry, its word included; zero-length entries are never touched.
+ * With r = 2 the code has distance 3: two bad bytes at one position can imitate a third shard
+ * (hbec_locate_plan_mixed's caveat) and the object then holds a consistent but wrong byte;
+ * the object's ETag (hbec_etag_plan_mixed) is what catches it.
+ * Errors, all found before anything is queued: hbec_glue_plan_mixed's, with the same
+ * precedence and messages; then a null d_fixed for a plan with entries; then d_fixed's words
+ * inside a destination range.
+ * k <= 12 with m <= 4 and shards below 2^31 - 64 KiB run as one launch (per 2^31 - 1 tiles)
+ * whatever the entries, masks or lengths; a call with nothing to write launches nothing.
+ * Other shapes are NOT checked: they get HBEC_COR_SKIPPED and are glued by
+ * hbec_glue_plan_mixed's per-entry route, counted in per_stripe_calls below.  Queued on
+ * hip_stream and not waited for; calls on one plan take turns with the other _mixed calls. */
+int hbec_glue_plan_checked(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                           const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens,
+                           uint32_t* d_fixed, void* hip_stream);
+/* The object-level form for hbec_plan_files plans: objects are cut into entries exactly as
+ * hbec_glue_plan_files cuts them (ecGlue, ecutils.go:134-186; surplus shards as above,
+ * ecobj.go:173-203), with its errors, and then it is hbec_glue_plan_checked.  pattern_of and
+ * d_fixed stay per ENTRY. */
+int hbec_glue_plan_files_checked(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                                 uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                                 const uint8_t* patterns, uint32_t n_patterns, const uint32_t* pattern_of,
+                                 void* const* object_dsts, uint32_t* d_fixed, void* hip_stream);
+/* launches since load of the checked glue kernel (ecobj.go:173-203), and copies and applies of the per-entry route */
+int hbec_glue_checked_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
+/* shard bytes per wave tile of the checked glue kernel (ecobj.go:173-203) */
+int hbec_glue_checked_tile_bytes(void);
+/* test hook for the checked glue (ecobj.go:173-203), as hbec_set_mixed_plan_chunk_tiles */
+int hbec_set_glue_checked_chunk_tiles(uint64_t tiles);
+
 /* Any byte range of every entry of a plan in one call: the decode of a ranged GET
  * (ecObject.CopyRange, ecobj.go:207-267) over ecGlue's layout (ecutils.go:134-186) for a
  * batch whose shards are in device memory, degraded or not.  patterns / n_patterns /
