@@ -719,6 +719,56 @@ class StripePlan:
             patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d,
             st.ctypes.data_as(C.POINTER(C.c_uint64)), en.ctypes.data_as(C.POINTER(C.c_uint64)), _stream_ptr(stream)))
 
+    def glue_range_checked(self, present, dsts, starts, lens, fixed, stream=None):
+        """glue_range that reads every PRESENT shard once, checks the surplus
+        ones and writes the range's bytes of the corrected codeword
+        (hbec_glue_plan_range_checked): read-repair on a ranged GET.  No shard
+        is written.  The shard positions that hold a wanted byte in some data
+        shard are examined by correct_mixed's rule, and no others: a bad byte
+        outside them is neither reported nor corrected.  ``fixed`` as in
+        glue_checked: COR_BAD, COR_LEFT, COR_NOTHING (exactly k present: glued
+        as glue_range does), COR_SKIPPED (the other route: glued, not checked)
+        and, in bits 0..15, the shards a byte was taken as corrected in.
+        lens[i] = 0 skips the entry and its word."""
+        import numpy as np
+
+        patterns, pattern_of = self._patterns(present)
+        if len(dsts) != self._n or len(starts) != self._n or len(lens) != self._n:
+            raise ValueError("dsts, starts and lens need one element per entry")
+        d = (C.c_void_p * max(1, self._n))(*[int(a) for a in dsts])
+        st, ln = np.zeros(max(1, self._n), np.uint64), np.zeros(max(1, self._n), np.uint64)
+        st[:self._n] = [int(x) for x in starts]
+        ln[:self._n] = [int(x) for x in lens]
+        check(N.lib().hbec_glue_plan_range_checked(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, st.ctypes.data_as(C.POINTER(C.c_uint64)),
+            ln.ctypes.data_as(C.POINTER(C.c_uint64)), self._fixed_ptr(fixed), _stream_ptr(stream)))
+
+    def glue_range_files_checked(self, present, outs, starts, ends, fixed, stream=None):
+        """glue_range_checked for a ``files=`` plan, object by object
+        (hbec_glue_plan_files_range_checked): ranges are cut as glue_range_files
+        cuts them; ``present`` and ``fixed`` stay per ENTRY."""
+        import numpy as np
+
+        if getattr(self, "_content_lengths", None) is None:
+            raise ValueError("glue_range_files_checked needs a plan built from files=")
+        patterns, pattern_of = self._patterns(present)
+        n_obj = len(self._content_lengths)
+        if len(outs) != n_obj or len(starts) != n_obj or len(ends) != n_obj:
+            raise ValueError("outs, starts and ends need one element per object")
+        d = (C.c_void_p * max(1, n_obj))(*[int(a) for a in outs])
+        ln, st, en = (np.zeros(max(1, n_obj), np.uint64) for _ in range(3))
+        ln[:n_obj] = self._content_lengths
+        st[:n_obj] = [int(x) for x in starts]
+        en[:n_obj] = [int(x) for x in ends]
+        object_start = np.ascontiguousarray(self.object_start, dtype=np.uint32)
+        check(N.lib().hbec_glue_plan_files_range_checked(
+            self.enc.handle, self._h, object_start.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
+            ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), patterns.ctypes.data_as(N._U8P),
+            patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d,
+            st.ctypes.data_as(C.POINTER(C.c_uint64)), en.ctypes.data_as(C.POINTER(C.c_uint64)),
+            self._fixed_ptr(fixed), _stream_ptr(stream)))
+
     def _etag_tensors(self, n_slots, per, digests, expected, bad, filter):
         """The shape and dtype checks of etag_mixed / etag_files."""
         import torch
@@ -938,6 +988,25 @@ def glue_range_tile_bytes() -> int:
 def set_glue_range_chunk_tiles(tiles: int) -> None:
     """Test hook: range kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_glue_range_chunk_tiles(int(tiles)))
+
+
+def glue_range_checked_stats():
+    """Since load, for StripePlan.glue_range_checked / glue_range_files_checked:
+    launches of the checked range kernel (`kernel_launches`) and, on the
+    per-entry route (glued, not checked), copies and applies (`per_stripe_calls`)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(N.lib().hbec_glue_range_checked_stats(C.byref(a), C.byref(b)))
+    return {"kernel_launches": a.value, "per_stripe_calls": b.value}
+
+
+def glue_range_checked_tile_bytes() -> int:
+    """Shard bytes per wave tile of the checked range kernel."""
+    return int(N.lib().hbec_glue_range_checked_tile_bytes())
+
+
+def set_glue_range_checked_chunk_tiles(tiles: int) -> None:
+    """Test hook: checked range kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_glue_range_checked_chunk_tiles(int(tiles)))
 
 
 def etag_plan_stats():

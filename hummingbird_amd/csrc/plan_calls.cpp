@@ -26,7 +26,10 @@
 // a start beside each length.  The glue that reads every present shard, checks the
 // surplus ones and corrects what it writes (hbec_glue_plan_checked and
 // hbec_glue_plan_files_checked; gluecheck.h, gluecheck.hip) stages glue's
-// destinations beside records of its own.  The ETag of every object (hbec_etag_plan_mixed and
+// destinations beside records of its own, and its ranged form
+// (hbec_glue_plan_range_checked and hbec_glue_plan_files_range_checked;
+// gluerangecheck.h, gluerangecheck.hip) stages the range call's triples beside
+// the same records.  The ETag of every object (hbec_etag_plan_mixed and
 // hbec_etag_plan_files; etag.h, etag.hip) decodes what is missing through that
 // call into scratch and hashes the object bytes where they lie, on the hash
 // calls' records.
@@ -49,6 +52,7 @@
 #include "glue.h"
 #include "gluecheck.h"
 #include "gluerange.h"
+#include "gluerangecheck.h"
 #include "hashfiles.h"
 #include "hashplan.h"
 #include "heal.h"
@@ -73,7 +77,7 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kGlueChecked, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kGlueChecked, kGlueRangeChecked, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
     std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal, correct); chains (hash calls)
@@ -1201,13 +1205,13 @@ int glue_plan_files_checked(hbec_codec* codec, const hbec_plan* plan, const uint
 // positions [A, B) their windows span (GF apply is bytewise): straight into the
 // destination where a shard's window is all of [A, B), through scratch and a
 // clipped copy where it is not.  Every copy and every apply counts as a
-// per-stripe call.
+// per-stripe call of the call `c`.
 int glue_range_other_entry(const hbec_plan* plan, uint32_t i, const uint8_t* mask, const ShardSet& out, uint64_t dst,
-                           uint64_t s, uint64_t len, hipStream_t stream) {
+                           uint64_t s, uint64_t len, hipStream_t stream, Call c = kGlueRange) {
     const int k = plan->k;
     const uint64_t S = plan->src[i].shard_len, e = s + len;
     auto copy = [&](uint64_t to, uint64_t from, uint64_t bytes) -> int {
-        count(g_calls[kGlueRange].second);
+        count(g_calls[c].second);
         const hipError_t err = hipMemcpyAsync(reinterpret_cast<void*>(to), reinterpret_cast<const void*>(from), bytes,
                                               hipMemcpyDeviceToDevice, stream);
         return err == hipSuccess ? HBEC_OK : hip_fail(err, "hipMemcpyAsync (glue range)");
@@ -1249,7 +1253,7 @@ int glue_range_other_entry(const hbec_plan* plan, uint32_t i, const uint8_t* mas
         vout[t] = hbec_view{reinterpret_cast<void*>(at), 0};
         std::memcpy(rows.data() + t * (size_t)k, out.rows.data() + q * (size_t)k, (size_t)k);
     }
-    count(g_calls[kGlueRange].second);
+    count(g_calls[c].second);
     int rc = hbec::apply_views((int)sel.size(), k, rows.data(), vin.data(), vout.data(), 1, B - A, stream);
     for (size_t t = 0; t < sel.size() && !rc; ++t) {
         if (whole(sel[t])) continue;
@@ -1261,17 +1265,15 @@ int glue_range_other_entry(const hbec_plan* plan, uint32_t i, const uint8_t* mas
     return rc;
 }
 
-int glue_plan_range(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
-                    const uint32_t* pattern_of, void* const* dsts, const uint64_t* starts, const uint64_t* lens,
-                    hipStream_t stream) {
-    std::vector<PlanPattern> pats;
-    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
-    if (rc) return rc;
+// What hbec_glue_plan_range checks of its ranges and destinations, after the
+// patterns' checks; hbec_glue_plan_range_checked makes the same.  *any: some
+// entry has bytes asked for.
+int check_range_dsts(const hbec_plan* plan, void* const* dsts, const uint64_t* starts, const uint64_t* lens,
+                     bool* any) {
     if (!dsts || !starts || !lens) return fail(HBEC_ERR_INVALID_ARG, "null argument");
     const int k = plan->k, n = k + plan->m;
-    const uint64_t n_src = plan->n_src;
-    bool any = false;
-    for (uint64_t i = 0; i < n_src; ++i) {  // zero-length entries too
+    *any = false;
+    for (uint64_t i = 0; i < plan->n_src; ++i) {  // zero-length entries too
         const uint64_t S = plan->src[i].shard_len, len = lens[i];
         if (!len) continue;  // whatever starts[i] and dsts[i] are
         const uint64_t dst = reinterpret_cast<uintptr_t>(dsts[i]);
@@ -1282,9 +1284,36 @@ int glue_plan_range(hbec_codec* codec, const hbec_plan* plan, const uint8_t* pat
             if (hbec::glue_overlaps(dst, len, shard_addr(plan, (uint32_t)i, sh), S))
                 return fail(HBEC_ERR_INVALID_ARG, "destination overlaps shard " + std::to_string(sh) +
                                                       " of its own entry (entry " + std::to_string(i) + ")");
-        any = true;
+        *any = true;
     }
+    return HBEC_OK;
+}
+
+// {address, start, length} per source entry, 64 bits each, low word first,
+// appended to a call's staging words
+size_t stage_ranges(const hbec_plan* plan, void* const* dsts, const uint64_t* starts, const uint64_t* lens,
+                    std::vector<uint32_t>& stage) {
+    const size_t range_at = stage.size();
+    stage.resize(range_at + 6 * (size_t)plan->n_src);
+    for (uint64_t i = 0; i < plan->n_src; ++i) {
+        const uint64_t v[3] = {reinterpret_cast<uintptr_t>(dsts[i]), starts[i], lens[i]};
+        uint32_t* d = stage.data() + range_at + 6 * i;
+        for (int q = 0; q < 3; ++q) d[2 * q] = (uint32_t)v[q], d[2 * q + 1] = (uint32_t)(v[q] >> 32);
+    }
+    return range_at;
+}
+
+int glue_plan_range(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                    const uint32_t* pattern_of, void* const* dsts, const uint64_t* starts, const uint64_t* lens,
+                    hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    bool any = false;
+    rc = check_range_dsts(plan, dsts, starts, lens, &any);
+    if (rc) return rc;
     if (!any) return HBEC_OK;  // nothing asked for
+    const int k = plan->k, n = k + plan->m;
     bool used = false;
     rc = resolve_patterns(codec, patterns, true, true, false, pats, &used);
     if (rc) return rc;
@@ -1312,13 +1341,7 @@ int glue_plan_range(hbec_codec* codec, const hbec_plan* plan, const uint8_t* pat
                 rmax = std::max(rmax, r);
                 return ((uint32_t)r << hbec::kMPatShift) | pp.rec;
             });
-        const size_t range_at = stage.size();
-        stage.resize(range_at + 6 * (size_t)n_src);
-        for (uint64_t i = 0; i < n_src; ++i) {
-            const uint64_t v[3] = {reinterpret_cast<uintptr_t>(dsts[i]), starts[i], lens[i]};
-            uint32_t* d = stage.data() + range_at + 6 * i;
-            for (int q = 0; q < 3; ++q) d[2 * q] = (uint32_t)v[q], d[2 * q + 1] = (uint32_t)(v[q] >> 32);
-        }
+        const size_t range_at = stage_ranges(plan, dsts, starts, lens, stage);
         if (rmax >= 0) {
             int cus = 0;
             rc = current_cus(&cus);
@@ -1345,17 +1368,21 @@ int glue_plan_range(hbec_codec* codec, const hbec_plan* plan, const uint8_t* pat
 
 // ---- a byte range of whole objects of a files plan (hbec_glue_plan_files_range) ----
 
-int glue_plan_files_range(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
-                          const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
-                          uint32_t n_patterns, const uint32_t* pattern_of, void* const* object_dsts,
-                          const uint64_t* range_starts, const uint64_t* range_ends, hipStream_t stream) {
+// hbec_glue_plan_files_range's checks of its own and the cut of every object's
+// range into its entries' (gr_files_cut); hbec_glue_plan_files_range_checked
+// makes the same.
+int glue_files_ranges(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                      const uint64_t* content_lengths, uint64_t chunk_size, void* const* object_dsts,
+                      const uint64_t* range_starts, const uint64_t* range_ends, std::vector<void*>& dsts,
+                      std::vector<uint64_t>& starts, std::vector<uint64_t>& lens) {
     if (!codec || !plan || !content_lengths || !object_dsts || !range_starts || !range_ends)
         return fail(HBEC_ERR_INVALID_ARG, "null argument");
     const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
     if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
     const uint64_t n_src = plan->n_src;
-    std::vector<void*> dsts((size_t)std::max<uint64_t>(1, n_src), nullptr);
-    std::vector<uint64_t> starts((size_t)std::max<uint64_t>(1, n_src), 0u), lens(starts);
+    dsts.assign((size_t)std::max<uint64_t>(1, n_src), nullptr);
+    starts.assign((size_t)std::max<uint64_t>(1, n_src), 0u);
+    lens = starts;
     if (n_src) {
         if (const char* why = hbec::files_check_objects(object_start, n_objects, n_src))
             return fail(HBEC_ERR_INVALID_ARG, why);
@@ -1381,8 +1408,117 @@ int glue_plan_files_range(hbec_codec* codec, const hbec_plan* plan, const uint32
             }
         }
     }
+    return HBEC_OK;
+}
+
+int glue_plan_files_range(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                          const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
+                          uint32_t n_patterns, const uint32_t* pattern_of, void* const* object_dsts,
+                          const uint64_t* range_starts, const uint64_t* range_ends, hipStream_t stream) {
+    std::vector<void*> dsts;
+    std::vector<uint64_t> starts, lens;
+    const int rc = glue_files_ranges(codec, plan, object_start, n_objects, content_lengths, chunk_size, object_dsts,
+                                     range_starts, range_ends, dsts, starts, lens);
+    if (rc) return rc;
     return glue_plan_range(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), starts.data(), lens.data(),
                            stream);
+}
+
+// ---- any byte range with the surplus shards checked (hbec_glue_plan_range_checked) ----
+
+// hbec_glue_plan_range that reads every present shard: glue_plan_checked's
+// record per mask with a checked shard (gluecheck.h), glue_plan_range's own
+// where exactly k are present, so that such an entry is glued exactly as that
+// call glues it, the range call's triples, and correct's word per entry.  The
+// other route glues as glue_plan_range's does, checks nothing and says so.
+int glue_plan_range_checked(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                            const uint32_t* pattern_of, void* const* dsts, const uint64_t* starts,
+                            const uint64_t* lens, uint32_t* d_fixed, hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    bool any = false;
+    rc = check_range_dsts(plan, dsts, starts, lens, &any);
+    if (rc) return rc;
+    const int k = plan->k, n = k + plan->m;
+    const uint64_t n_src = plan->n_src;
+    if (!d_fixed && n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    for (uint64_t i = 0; i < n_src; ++i)
+        if (hbec::glue_overlaps(reinterpret_cast<uintptr_t>(dsts[i]), lens[i], reinterpret_cast<uintptr_t>(d_fixed),
+                                4 * n_src))
+            return fail(HBEC_ERR_INVALID_ARG, "d_fixed aliases a destination (entry " + std::to_string(i) + ")");
+    if (!any) return HBEC_OK;  // nothing asked for
+    bool used = false;
+    rc = resolve_patterns(codec, patterns, true, true, true, pats, &used);
+    if (rc) return rc;
+    rc = mixed_plan_device(plan);
+    if (rc) return rc;
+
+    if (plan->n_mtiles > 0) {
+        int amax = -1;
+        std::vector<int> data((size_t)k);
+        for (int j = 0; j < k; ++j) data[j] = j;
+        std::vector<uint32_t> stage;
+        const size_t rec_words = stage_patterns(
+            plan, pats, pattern_of, stage,
+            [&](PlanPattern& pp) {
+                const ShardSet &o = pp.out, &c = pp.chk;
+                if (!c.idx.empty())
+                    pp.rec = hbec::gc_record(stage, k, c.surv.data(), c.idx.data(), (int)c.idx.size(), c.rows.data(),
+                                             o.idx.data(), (int)o.idx.size(), o.rows.data());
+                else  // exactly k present: glue_plan_range's record
+                    pp.rec = o.idx.empty() ? hbec::mp_pattern(stage, k, data.data(), nullptr, 0, nullptr)
+                                           : hbec::mp_pattern(stage, k, o.surv.data(), o.idx.data(),
+                                                              (int)o.idx.size(), o.rows.data());
+            },
+            [&](uint64_t i, const PlanPattern& pp) {
+                const uint64_t S = plan->src[i].shard_len;
+                if (S == 0 || !hbec::pos32_shard(S) || lens[i] == 0) return hbec::kGlueSkip;  // mp_build's route
+                const int r = (int)pp.chk.idx.size(), o = (int)pp.out.idx.size();
+                amax = std::max(amax, hbec::grc_rows(r, o));
+                return hbec::grc_word(r, o, pp.rec);
+            });
+        const size_t range_at = stage_ranges(plan, dsts, starts, lens, stage);
+        if (amax >= 0) {
+            int cus = 0;
+            rc = current_cus(&cus);
+            if (rc) return rc;
+            rc = staged_launches(plan, stage, stream, [&](const uint32_t* d_pats) {
+                return walk_chunks(kGlueRangeChecked, plan->n_mtiles, "launch gf_range_checked",
+                                   [&](uint64_t t0, uint32_t nt) {
+                                       return (hipError_t)hbec::launch_glue_range_checked(
+                                           k, amax, plan->d_mrecs, plan->d_mtiles + t0, nt, d_pats + rec_words,
+                                           d_pats + range_at, d_pats, d_fixed, cus, stream, plan->shards);
+                                   });
+            });
+            if (rc) return rc;
+        }
+    }
+    // the other route, one entry at a time (any k, m, S): glued, not checked
+    for (uint32_t i : plan->mp_other) {
+        if (!lens[i]) continue;
+        rc = glue_range_other_entry(plan, i, patterns + (size_t)pattern_of[i] * n, pats[pattern_of[i]].out,
+                                    reinterpret_cast<uintptr_t>(dsts[i]), starts[i], lens[i], stream,
+                                    kGlueRangeChecked);
+        if (rc) return rc;
+        const hipError_t e = hbec::launch_vm_or(d_fixed + i, hbec::kCorSkipped, stream);
+        if (e != hipSuccess) return hip_fail(e, "launch gf_vm_or");
+    }
+    return HBEC_OK;
+}
+
+int glue_plan_files_range_checked(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                                  uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                                  const uint8_t* patterns, uint32_t n_patterns, const uint32_t* pattern_of,
+                                  void* const* object_dsts, const uint64_t* range_starts, const uint64_t* range_ends,
+                                  uint32_t* d_fixed, hipStream_t stream) {
+    std::vector<void*> dsts;
+    std::vector<uint64_t> starts, lens;
+    const int rc = glue_files_ranges(codec, plan, object_start, n_objects, content_lengths, chunk_size, object_dsts,
+                                     range_starts, range_ends, dsts, starts, lens);
+    if (rc) return rc;
+    return glue_plan_range_checked(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), starts.data(),
+                                   lens.data(), d_fixed, stream);
 }
 
 // ---- the ETag of every object from its shards (hbec_etag_plan_mixed, hbec_etag_plan_files) ----
@@ -2090,6 +2226,37 @@ int hbec_glue_range_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
 
 int hbec_set_glue_range_chunk_tiles(uint64_t tiles) {
     return set_chunk_tiles("hbec_set_glue_range_chunk_tiles", kGlueRange, tiles);
+}
+
+int hbec_glue_plan_range_checked(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns,
+                                 uint32_t n_patterns, const uint32_t* pattern_of, void* const* dsts,
+                                 const uint64_t* starts, const uint64_t* lens, uint32_t* d_fixed, void* hip_stream) {
+    return hbec::guarded("hbec_glue_plan_range_checked", [&]() -> int {
+        return glue_plan_range_checked(codec, plan, patterns, n_patterns, pattern_of, dsts, starts, lens, d_fixed,
+                                       static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_glue_plan_files_range_checked(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                                       uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                                       const uint8_t* patterns, uint32_t n_patterns, const uint32_t* pattern_of,
+                                       void* const* object_dsts, const uint64_t* range_starts,
+                                       const uint64_t* range_ends, uint32_t* d_fixed, void* hip_stream) {
+    return hbec::guarded("hbec_glue_plan_files_range_checked", [&]() -> int {
+        return glue_plan_files_range_checked(codec, plan, object_start, n_objects, content_lengths, chunk_size,
+                                             patterns, n_patterns, pattern_of, object_dsts, range_starts, range_ends,
+                                             d_fixed, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_glue_range_checked_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
+    return call_stats("hbec_glue_range_checked_stats", kGlueRangeChecked, kernel_launches, per_stripe_calls);
+}
+
+int hbec_glue_range_checked_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
+
+int hbec_set_glue_range_checked_chunk_tiles(uint64_t tiles) {
+    return set_chunk_tiles("hbec_set_glue_range_checked_chunk_tiles", kGlueRangeChecked, tiles);
 }
 
 int hbec_etag_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,

@@ -888,6 +888,72 @@ int hbec_glue_range_tile_bytes(void);
 /* test hook, as hbec_set_mixed_plan_chunk_tiles */
 int hbec_set_glue_range_chunk_tiles(uint64_t tiles);
 
+/* hbec_glue_plan_range with every PRESENT shard read once, the surplus ones checked at the
+ * shard positions the range touches and the bytes they prove wrong corrected in what is
+ * written: read-repair on a ranged GET (ecObject.CopyRange, ecobj.go:207-267, over ecGlue's
+ * layout, ecutils.go:134-186, with the surplus shards a GET has in hand, ecobj.go:173-203,
+ * main.go:233-241).  It is hbec_glue_plan_checked for any byte range: NO byte of any shard
+ * is stored, so the shard buffers may be a cache shared with other readers.
+ * patterns / n_patterns / pattern_of / dsts / starts / lens: exactly those of
+ * hbec_glue_plan_range.  Per entry i the survivors are the first k present shards and the
+ * checked shards the other present ones, r of them, as in hbec_check_rows.  With
+ * s = starts[i] and e = s + lens[i], the shard positions examined are exactly P: the
+ * positions that hold a wanted byte in some data shard, which is hbec_glue_plan_range's set
+ * of wanted positions, at most two intervals.  The rule at each is
+ * hbec_correct_plan_mixed's, unchanged.  With s = 0 P is hbec_glue_plan_checked's
+ * x < min(S_i, lens[i]), and the bytes and the word are that call's.  A bad byte at a
+ * position outside P is neither reported nor corrected.
+ * The call writes D'_i[s, e) to [dsts[i], dsts[i] + lens[i]) and stores nothing else: no
+ * shard byte and no byte outside that range.  D'_i is hbec_glue_plan_mixed's D_i taken from
+ * the entry as hbec_correct_plan_mixed would leave it over P: a present data shard t that is
+ * the candidate at x contributes stored ^ e, where x lies in t's window [lo_t, hi_t)
+ * (hbec_glue_plan_range); a missing data shard d with x in its window contributes what
+ * ReconstructData computes from the corrected survivors; a candidate among the checked
+ * shards, among parity survivors or in a data shard whose window does not hold x changes no
+ * written byte of that shard; a position with no candidate (r = 1, or two bad bytes in one
+ * column with r >= 3) contributes what hbec_glue_plan_range writes.
+ * d_fixed: uint32, device, one word per source entry, zeroed by the caller, only ever ORed
+ * into; it must not alias a destination.  The bits are hbec_glue_plan_checked's: HBEC_COR_BAD
+ * and HBEC_COR_LEFT as there; bits 0..15 name every shard that was the candidate at an
+ * examined position (the shards themselves are unchanged); HBEC_COR_NOTHING: exactly k
+ * present, the entry is glued exactly as hbec_glue_plan_range glues it, gathered tiles
+ * included; HBEC_COR_SKIPPED on the other route.  lens[i] = 0 skips the entry, its word
+ * included; zero-length entries are never touched.
+ * With r = 2 the code has distance 3: two bad bytes at one position can imitate a third shard
+ * (hbec_locate_plan_mixed's caveat) and the range then holds a consistent but wrong byte;
+ * the object's ETag (hbec_etag_plan_mixed) is what catches it.
+ * What is read: every present shard of the entry at the positions of every tile that holds a
+ * position of P, and no byte outside [shard, shard + S) (16-byte blocks are loaded whole
+ * where they hold such a byte).  A range inside one data shard therefore reads k + r shards
+ * where hbec_glue_plan_range reads one: the price of the check.
+ * Errors, all found before anything is queued: hbec_glue_plan_range's, with the same
+ * precedence and messages; then a null d_fixed for a plan with entries; then d_fixed's words
+ * inside a destination range.
+ * k <= 12 with m <= 4 and shards below 2^31 - 64 KiB run as one launch (per 2^31 - 1 tiles)
+ * whatever the entries, masks or ranges; a call with nothing to write launches nothing.
+ * Other shapes are NOT checked: they get HBEC_COR_SKIPPED and are glued by
+ * hbec_glue_plan_range's per-entry route, counted in per_stripe_calls below.  Queued on
+ * hip_stream and not waited for; calls on one plan take turns with the other _mixed calls. */
+int hbec_glue_plan_range_checked(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns,
+                                 uint32_t n_patterns, const uint32_t* pattern_of, void* const* dsts,
+                                 const uint64_t* starts, const uint64_t* lens, uint32_t* d_fixed, void* hip_stream);
+/* The object-level form for hbec_plan_files plans (ecobj.go:207-267 over ecutils.go:134-186;
+ * surplus shards as above, ecobj.go:173-203): hbec_glue_plan_files_range's checks, with its
+ * errors, and its cut of every object's range into its entries', and then it is
+ * hbec_glue_plan_range_checked.  pattern_of and d_fixed stay per ENTRY. */
+int hbec_glue_plan_files_range_checked(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                                       uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                                       const uint8_t* patterns, uint32_t n_patterns, const uint32_t* pattern_of,
+                                       void* const* object_dsts, const uint64_t* range_starts,
+                                       const uint64_t* range_ends, uint32_t* d_fixed, void* hip_stream);
+/* launches since load of the checked range kernel (ecobj.go:207-267, ecobj.go:173-203), and copies and applies of
+ * the per-entry route */
+int hbec_glue_range_checked_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
+/* shard bytes per wave tile of the checked range kernel (ecobj.go:207-267, ecobj.go:173-203) */
+int hbec_glue_range_checked_tile_bytes(void);
+/* test hook for the checked range glue (ecobj.go:207-267, ecobj.go:173-203), as hbec_set_mixed_plan_chunk_tiles */
+int hbec_set_glue_range_checked_chunk_tiles(uint64_t tiles);
+
 /* The ETag of every entry of a plan from its shards, degraded or not: the MD5 of the object's
  * own bytes, which every shard carries in its metadata (ecengine.go:320-321,
  * indexdb.go:739-740,768-769, ecobj.go:415-417) and the reference's auditor checks for
