@@ -152,6 +152,9 @@ _SIG = [
     ("hbec_repair_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_repair_plan_tile_bytes", C.c_int, []),
     ("hbec_set_repair_plan_chunk_tiles", C.c_int, [C.c_uint64]),
+    ("hbec_repair_plan_wide", C.c_int, [_P, _P, _U8P, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, _P, _P]),
+    ("hbec_repair_wide_stats", C.c_int, [C.POINTER(C.c_uint64)]),
+    ("hbec_set_repair_wide_chunk_tiles", C.c_int, [C.c_uint32]),
     ("hbec_heal_plan_mixed", C.c_int, [_P, _P, _U8P, C.c_uint32, C.POINTER(C.c_uint32), _P, _P, _P]),
     ("hbec_heal_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_heal_plan_tile_bytes", C.c_int, []),

@@ -327,6 +327,25 @@ class StripePlan:
             pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), int(data_only), C.c_void_p(flags.data_ptr()),
             _stream_ptr(stream)))
 
+    def repair_wide(self, present, flags, data_only=False, stream=None):
+        """repair_mixed for wide stripes, 1 <= k <= 32 with m <= 4 (16+4, 17+3,
+        20+4), in one launch on any kind of plan (hbec_repair_plan_wide): the
+        same arguments, and the same buffers and flags after the call.  Above
+        k = 12 repair_mixed repairs one stripe at a time.  Other shapes, and
+        plans with a shard of 2^31 - 64 KiB or more, raise: there is no
+        per-stripe route.  Queued on the stream."""
+        import torch
+
+        if flags.dtype != torch.uint32 and flags.dtype != torch.int32:
+            raise ValueError("flags must be a 32-bit integer tensor")
+        if not flags.is_cuda or not flags.is_contiguous() or flags.numel() < self._n:
+            raise ValueError("flags must be a contiguous CUDA tensor with one entry per stripe")
+        patterns, pattern_of = self._patterns(present)
+        check(N.lib().hbec_repair_plan_wide(
+            self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
+            pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), int(data_only), C.c_void_p(flags.data_ptr()),
+            _stream_ptr(stream)))
+
     def locate_mixed(self, present, where, flags=None, stream=None):
         """Name the corrupt shard of every inconsistent entry: ``present`` is an
         [n, k+m] array as in verify_mixed (None: every shard present), ``where``
@@ -1144,6 +1163,19 @@ def repair_plan_tile_bytes() -> int:
 def set_repair_plan_chunk_tiles(tiles: int) -> None:
     """Test hook: repair kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_repair_plan_chunk_tiles(int(tiles)))
+
+
+def repair_wide_stats():
+    """Since load, for StripePlan.repair_wide: launches of the wide repair
+    kernel (`kernel_launches`); the call has no other route."""
+    a = C.c_uint64()
+    check(N.lib().hbec_repair_wide_stats(C.byref(a)))
+    return {"kernel_launches": a.value}
+
+
+def set_repair_wide_chunk_tiles(tiles: int) -> None:
+    """Test hook: wide repair kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_repair_wide_chunk_tiles(int(tiles)))
 
 
 def heal_plan_stats():

@@ -814,6 +814,8 @@ void hbec_plan_free(hbec_plan* plan) {
     if (plan->d_mtiles) (void)hipFree(plan->d_mtiles);
     if (plan->d_sprecs) (void)hipFree(plan->d_sprecs);
     if (plan->d_sptiles) (void)hipFree(plan->d_sptiles);
+    if (plan->d_rwrecs) (void)hipFree(plan->d_rwrecs);
+    if (plan->d_rwtiles) (void)hipFree(plan->d_rwtiles);
     if (plan->d_mstage) (void)hipFree(plan->d_mstage);
     if (plan->d_heal) (void)hipFree(plan->d_heal);
     if (plan->d_hrecs) (void)hipFree(plan->d_hrecs);

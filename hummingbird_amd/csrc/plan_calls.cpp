@@ -7,6 +7,9 @@
 // (hbec_locate_plan_mixed; locate.h, locate.hip), the call that rebuilds and
 // checks in one pass (hbec_repair_plan_mixed; repair.h, repair.hip) and the call
 // that rebuilds the shard locate named (hbec_heal_plan_mixed; heal.h, heal.hip).
+// The rebuild-and-check call for stripes of up to 32 data shards
+// (hbec_repair_plan_wide; repairwide.h, repairwide.hip) walks the same list, or
+// one of its own where k > 12, with records of its own.
 // The call that corrects bad bytes column by column (hbec_correct_plan_mixed;
 // correct.h, correct.hip) walks them too, with records of its own.
 // The ShardHash audit of a plan (hbec_hash_plan_mixed; hashplan.h, hashplan.hip)
@@ -62,6 +65,7 @@
 #include "mixedplan.h"
 #include "plan_internal.h"
 #include "repair.h"
+#include "repairwide.h"
 #include "shardplan.h"
 #include "splitplan.h"
 #include "splitselect.h"
@@ -77,7 +81,7 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kGlueChecked, kGlueRangeChecked, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kGlueChecked, kGlueRangeChecked, kRepairWide, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
     std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal, correct); chains (hash calls)
@@ -203,12 +207,14 @@ Queued walk_chunks(Call c, uint64_t n_tiles, const char* what, Launch&& launch, 
 // The device side of the calls that walk a plan's {entry, tile} list, built
 // once: records and list into the plan's fields given, the entries of the other
 // route into *other.  route_m: the parity count the entries are routed by.
+// wide: every entry is listed whatever k is (rw_build), and *other stays empty.
 int walk_list_device(const hbec_plan* p, int route_m, bool* built, hbec::MRec** d_recs, hbec::MTile** d_tiles,
-                     uint64_t* n_tiles, std::vector<uint32_t>* other) {
+                     uint64_t* n_tiles, std::vector<uint32_t>* other, bool wide = false) {
     std::lock_guard<std::mutex> lk(p->mp_mu);
     if (*built) return HBEC_OK;
     hbec::MixedPlanRecs mr;
-    if (!hbec::mp_build(mr, p->k, route_m, p->src, hbec::mixed_plan_tile_bytes()))
+    if (!(wide ? hbec::rw_build(mr, p->src, hbec::mixed_plan_tile_bytes())
+               : hbec::mp_build(mr, p->k, route_m, p->src, hbec::mixed_plan_tile_bytes())))
         return fail(HBEC_ERR_INVALID_ARG, "plan too large (>= 2^31 tiles)");
     if (!mr.tiles.empty()) {
         int rc = upload(mr.recs, d_recs, "plan mixed records");
@@ -554,6 +560,68 @@ int repair_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* p
         if (rc) return rc;
     }
     return HBEC_OK;
+}
+
+// ---- hbec_repair_plan_mixed's contract for 1 <= k <= 32 in one launch (hbec_repair_plan_wide) ----
+
+int repair_plan_wide(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                     const uint32_t* pattern_of, bool data_only, uint32_t* d_flags, hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    if (!d_flags && plan->n_src) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+    const int k = plan->k, m = plan->m;
+    // no per-stripe route: what the kernel does not take is refused
+    if (!hbec::rw_shape(k, m)) return fail(HBEC_ERR_INVALID_ARG, "hbec_repair_plan_wide takes 1 <= k <= 32 with 1 <= m <= 4");
+    for (uint64_t i = 0; i < plan->n_src; ++i)
+        if (!hbec::pos32_shard(plan->src[i].shard_len))
+            return fail(HBEC_ERR_INVALID_ARG, "shard of 2^31 - 64 KiB bytes or more (stripe " + std::to_string(i) + ")");
+    bool used = false;
+    rc = resolve_patterns(codec, patterns, true, data_only, true, pats, &used);
+    if (rc) return rc;
+    if (!used) return HBEC_OK;  // zero-length entries only
+    // k <= 12: the mixed family's records and list; wider: the call's own
+    const bool own = !hbec::mp_fast_shape(k, m);
+    std::vector<uint32_t> none;
+    rc = own ? walk_list_device(plan, m, &plan->rw_built, &plan->d_rwrecs, &plan->d_rwtiles, &plan->n_rwtiles, &none,
+                                true)
+             : mixed_plan_device(plan);
+    if (rc) return rc;
+    const hbec::MRec* d_recs = own ? plan->d_rwrecs : plan->d_mrecs;
+    const hbec::MTile* d_tiles = own ? plan->d_rwtiles : plan->d_mtiles;
+    const uint64_t n_tiles = own ? plan->n_rwtiles : plan->n_mtiles;
+    int cus = 0;
+    rc = current_cus(&cus);
+    if (rc) return rc;
+    // the records of the masks with a shard to rebuild or to check, one stride
+    // apart, and one word per source entry; one launch per chunk of the list, of
+    // the instance for the largest row total in use
+    int amax = 1;  // exactly-k entries with nothing to rebuild alone: any instance sets their bit
+    for (const PlanPattern& pp : pats)
+        if (pp.uses) amax = std::max(amax, (int)(pp.out.idx.size() + pp.chk.idx.size()));
+    const uint32_t stride = hbec::rw_record_words(k, amax);
+    uint32_t n_rec = 0;
+    std::vector<uint32_t> stage;
+    const size_t rec_words = stage_patterns(
+        plan, pats, pattern_of, stage,
+        [&](PlanPattern& pp) {
+            const ShardSet &o = pp.out, &c = pp.chk;
+            if (o.idx.size() + c.idx.size() == 0) return;
+            pp.rec = n_rec++;
+            stage.resize((size_t)n_rec * stride, 0u);
+            hbec::rw_pattern(stage.data() + (size_t)pp.rec * stride, k, c.surv.data(), o.idx.data(), (int)o.idx.size(),
+                             o.rows.data(), c.idx.data(), (int)c.idx.size(), c.rows.data());
+        },
+        [&](uint64_t i, const PlanPattern& pp) {
+            if (plan->src[i].shard_len == 0) return 0u;
+            return hbec::rw_word((int)pp.out.idx.size(), (int)pp.chk.idx.size(), pp.rec);
+        });
+    return staged_launches(plan, stage, stream, [&](const uint32_t* d_pats) {
+        return walk_chunks(kRepairWide, n_tiles, "launch gf_repair_wide_plan", [&](uint64_t t0, uint32_t nt) {
+            return hbec::launch_repair_wide_plan(k, amax, stride, d_recs, d_tiles + t0, nt, d_pats + rec_words, d_pats,
+                                                 d_flags, cus, stream, plan->shards);
+        });
+    });
 }
 
 // ---- the corrupt shard of every inconsistent stripe (hbec_locate_plan_mixed) ----
@@ -2047,6 +2115,26 @@ int hbec_repair_plan_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
 
 int hbec_set_repair_plan_chunk_tiles(uint64_t tiles) {
     return set_chunk_tiles("hbec_set_repair_plan_chunk_tiles", kRepair, tiles);
+}
+
+int hbec_repair_plan_wide(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                          const uint32_t* pattern_of, int data_only, uint32_t* d_flags, void* hip_stream) {
+    return hbec::guarded("hbec_repair_plan_wide", [&]() -> int {
+        return repair_plan_wide(codec, plan, patterns, n_patterns, pattern_of, data_only != 0, d_flags,
+                                static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_repair_wide_stats(uint64_t* kernel_launches) {
+    return hbec::guarded("hbec_repair_wide_stats", [&]() -> int {
+        if (!kernel_launches) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *kernel_launches = g_calls[kRepairWide].launches.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_set_repair_wide_chunk_tiles(uint32_t tiles) {
+    return set_chunk_tiles("hbec_set_repair_wide_chunk_tiles", kRepairWide, tiles);
 }
 
 int hbec_locate_plan_mixed(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,

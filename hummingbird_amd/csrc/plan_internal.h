@@ -82,6 +82,13 @@ struct hbec_plan {
     mutable hbec::MTile* d_sptiles = nullptr;
     mutable uint64_t n_sptiles = 0;
     mutable std::vector<uint32_t> sp_other;
+    // hbec_repair_plan_wide on a plan of k > 12: mp_build lists no tile of it
+    // either, so the first such call builds records and a list of its own
+    // (mp_mu; repairwide.h rw_build).  With k <= 12 the call walks d_mrecs / d_mtiles.
+    mutable bool rw_built = false;
+    mutable hbec::MRec* d_rwrecs = nullptr;
+    mutable hbec::MTile* d_rwtiles = nullptr;
+    mutable uint64_t n_rwtiles = 0;
     // hbec_heal_plan_mixed: the records and tables of the last call's masks, on
     // the host (heal_mu) and on the device (d_heal, under mp_mu and ordered by
     // mp_ev like d_mstage).  They depend on (k, m) and the masks alone, and a

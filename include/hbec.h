@@ -521,6 +521,28 @@ int hbec_repair_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls
 int hbec_repair_plan_tile_bytes(void);
 /* test hook, as hbec_set_verify_mixed_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
 int hbec_set_repair_plan_chunk_tiles(uint64_t tiles);
+/* hbec_repair_plan_mixed for wide stripes: 1 <= k <= 32 with 1 <= m <= 4 (16+4, 17+3, 20+4,
+ * 32+4), at any alignment, shards of at most 2^31 - 64 KiB bytes, on every kind of plan, in
+ * one launch (per 2^31 - 1 tiles) whatever the number of stripes and patterns.  Arguments and
+ * meaning are hbec_repair_plan_mixed's, and so is every byte of the plan's buffers and every
+ * word of d_flags after the call: the missing shards of entry i rebuilt from its first k
+ * present shards (missing data shards only with data_only), every other present shard
+ * compared with what those k imply, d_flags[i] |= 1 on a mismatch and |= 2 when exactly k
+ * are present; no byte outside a rebuilt shard is written, and zero-length entries and
+ * entries with nothing to rebuild and nothing to check cost nothing.  With every shard
+ * present the call is hbec_verify_plan_mixed; with the flags ignored it is
+ * hbec_reconstruct_plan_mixed.  Every survivor byte is read once and every output byte
+ * written once, where hbec_repair_plan_mixed codes k > 12 one stripe at a time in passes of
+ * twelve inputs.  There is no per-stripe route: any other (k, m), or a plan that holds a
+ * longer shard, is HBEC_ERR_INVALID_ARG before anything is queued.  The other errors are
+ * hbec_repair_plan_mixed's, found before anything is queued likewise; up to 65536 patterns.
+ * Calls on one plan from different streams take turns with the _mixed calls. */
+int hbec_repair_plan_wide(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                          const uint32_t* pattern_of, int data_only, uint32_t* d_flags, void* hip_stream);
+/* launches since load of the wide repair kernel */
+int hbec_repair_wide_stats(uint64_t* kernel_launches);
+/* test hook, as hbec_set_repair_plan_chunk_tiles: tiles per launch of that kernel (0 = default) */
+int hbec_set_repair_wide_chunk_tiles(uint32_t tiles);
 /* The step that acts on hbec_locate_plan_mixed's answer, on the same plan and without a host
  * trip: every entry whose word names one shard is repaired again with that shard left out.
  * A sweep is hbec_repair_plan_mixed, hbec_locate_plan_mixed(d_flags) and this call, queued on
