@@ -172,6 +172,12 @@ _SIG = [
     ("hbec_glue_plan_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("hbec_glue_plan_tile_bytes", C.c_int, []),
     ("hbec_set_glue_plan_chunk_tiles", C.c_int, [C.c_uint64]),
+    ("hbec_glue_plan_wide", C.c_int, [_P, _P, _U8P, C.c_uint32, C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint64),
+                                      _P]),
+    ("hbec_glue_plan_files_wide", C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64),
+                                            C.c_uint64, _U8P, C.c_uint32, C.POINTER(C.c_uint32), _P, _P]),
+    ("hbec_glue_wide_stats", C.c_int, [C.POINTER(C.c_uint64)]),
+    ("hbec_set_glue_wide_chunk_tiles", C.c_int, [C.c_uint32]),
     ("hbec_glue_plan_checked", C.c_int, [_P, _P, _U8P, C.c_uint32, C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint64),
                                          _P, _P]),
     ("hbec_glue_plan_files_checked", C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64),

@@ -601,6 +601,19 @@ class StripePlan:
         what ReconstructData computes from the entry's first k present shards.
         No shard is written; lens[i] = 0 skips the entry, lens[i] <= k * S_i.
         Queued on the stream."""
+        self._glue_entries("hbec_glue_plan_mixed", present, dsts, lens, stream)
+
+    def glue_wide(self, present, dsts, lens, stream=None):
+        """glue_mixed for wide stripes, 1 <= k <= 32 with m <= 4 (16+4, 17+3,
+        20+4), in one launch on any kind of plan (hbec_glue_plan_wide): the same
+        arguments and the same bytes written.  Above k = 12 glue_mixed queues a
+        copy per present data shard and an apply per degraded entry.  An entry
+        whose missing data shards all lie beyond lens[i] reads only the data
+        shards with a byte wanted.  Other shapes, and plans with a shard of
+        2^31 - 64 KiB or more, raise: there is no per-entry route."""
+        self._glue_entries("hbec_glue_plan_wide", present, dsts, lens, stream)
+
+    def _glue_entries(self, symbol, present, dsts, lens, stream):
         import numpy as np
 
         patterns, pattern_of = self._patterns(present)
@@ -609,7 +622,7 @@ class StripePlan:
         d = (C.c_void_p * max(1, self._n))(*[int(a) for a in dsts])
         ln = np.zeros(max(1, self._n), np.uint64)
         ln[:self._n] = [int(x) for x in lens]
-        check(N.lib().hbec_glue_plan_mixed(
+        check(getattr(N.lib(), symbol)(
             self.enc.handle, self._h, patterns.ctypes.data_as(N._U8P), patterns.shape[0],
             pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, ln.ctypes.data_as(C.POINTER(C.c_uint64)),
             _stream_ptr(stream)))
@@ -619,10 +632,18 @@ class StripePlan:
         (hbec_glue_plan_files): object g is written whole, its content length
         in bytes, at the device address outs[g].  ``present`` stays per ENTRY
         ([object_start[-1], k+m]): a file may fail between two stripes."""
+        self._glue_objects("hbec_glue_plan_files", "glue_files", present, outs, stream)
+
+    def glue_files_wide(self, present, outs, stream=None):
+        """glue_files for wide stripes (hbec_glue_plan_files_wide): the objects
+        are cut as glue_files cuts them, and then it is glue_wide."""
+        self._glue_objects("hbec_glue_plan_files_wide", "glue_files_wide", present, outs, stream)
+
+    def _glue_objects(self, symbol, name, present, outs, stream):
         import numpy as np
 
         if getattr(self, "_content_lengths", None) is None:
-            raise ValueError("glue_files needs a plan built from files=")
+            raise ValueError(f"{name} needs a plan built from files=")
         patterns, pattern_of = self._patterns(present)
         n_obj = len(self._content_lengths)
         if len(outs) != n_obj:
@@ -631,7 +652,7 @@ class StripePlan:
         ln = np.zeros(max(1, n_obj), np.uint64)
         ln[:n_obj] = self._content_lengths
         starts = np.ascontiguousarray(self.object_start, dtype=np.uint32)
-        check(N.lib().hbec_glue_plan_files(
+        check(getattr(N.lib(), symbol)(
             self.enc.handle, self._h, starts.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
             ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), patterns.ctypes.data_as(N._U8P),
             patterns.shape[0], pattern_of.ctypes.data_as(C.POINTER(C.c_uint32)), d, _stream_ptr(stream)))
@@ -1176,6 +1197,19 @@ def repair_wide_stats():
 def set_repair_wide_chunk_tiles(tiles: int) -> None:
     """Test hook: wide repair kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_repair_wide_chunk_tiles(int(tiles)))
+
+
+def glue_wide_stats():
+    """Since load, for StripePlan.glue_wide / glue_files_wide: launches of the
+    wide glue kernel (`kernel_launches`); the call has no other route."""
+    a = C.c_uint64()
+    check(N.lib().hbec_glue_wide_stats(C.byref(a)))
+    return {"kernel_launches": a.value}
+
+
+def set_glue_wide_chunk_tiles(tiles: int) -> None:
+    """Test hook: wide glue kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_glue_wide_chunk_tiles(int(tiles)))
 
 
 def heal_plan_stats():

@@ -19,7 +19,9 @@
 // reads the same records and stages its chains and object table there too.
 // The object bytes of every entry from its shards (hbec_glue_plan_mixed and its
 // object-level form hbec_glue_plan_files; glue.h, glue.hip) walk Reconstruct's
-// records and list and stage a destination per entry beside the words.  The
+// records and list and stage a destination per entry beside the words; for
+// stripes of up to 32 data shards (hbec_glue_plan_wide, hbec_glue_plan_files_wide;
+// gluewide.h, gluewide.hip) they walk the wide repair's list with its records.  The
 // inverse, every entry's shards from its object bytes (hbec_split_plan and
 // hbec_split_plan_files; splitplan.h, splitplan.hip), walks them too and stages
 // a source per entry; with a writers mask per entry (hbec_split_plan_select and
@@ -56,6 +58,7 @@
 #include "gluecheck.h"
 #include "gluerange.h"
 #include "gluerangecheck.h"
+#include "gluewide.h"
 #include "hashfiles.h"
 #include "hashplan.h"
 #include "heal.h"
@@ -81,7 +84,7 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kGlueChecked, kGlueRangeChecked, kRepairWide, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kGlueChecked, kGlueRangeChecked, kRepairWide, kGlueWide, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
     std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal, correct); chains (hash calls)
@@ -1179,6 +1182,97 @@ int glue_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* ob
     return glue_plan_mixed(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), lens.data(), stream);
 }
 
+// ---- hbec_glue_plan_mixed's contract for 1 <= k <= 32 in one launch (hbec_glue_plan_wide) ----
+
+int glue_plan_wide(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                   const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens, hipStream_t stream) {
+    std::vector<PlanPattern> pats;
+    int rc = check_plan_patterns(codec, plan, patterns, n_patterns, pattern_of, pats);
+    if (rc) return rc;
+    bool any = false;
+    rc = check_glue_dsts(plan, dsts, dst_lens, &any);
+    if (rc) return rc;
+    const int k = plan->k, m = plan->m;
+    // no per-entry route: what the kernel does not take is refused
+    if (!hbec::rw_shape(k, m)) return fail(HBEC_ERR_INVALID_ARG, "hbec_glue_plan_wide takes 1 <= k <= 32 with 1 <= m <= 4");
+    for (uint64_t i = 0; i < plan->n_src; ++i)
+        if (!hbec::pos32_shard(plan->src[i].shard_len))
+            return fail(HBEC_ERR_INVALID_ARG, "shard of 2^31 - 64 KiB bytes or more (entry " + std::to_string(i) + ")");
+    if (!any) return HBEC_OK;  // nothing asked for
+    bool used = false;
+    rc = resolve_patterns(codec, patterns, true, true, false, pats, &used);
+    if (rc) return rc;
+    // k <= 12: the mixed family's records and list; wider: the wide repair's
+    const bool own = !hbec::mp_fast_shape(k, m);
+    std::vector<uint32_t> none;
+    rc = own ? walk_list_device(plan, m, &plan->rw_built, &plan->d_rwrecs, &plan->d_rwtiles, &plan->n_rwtiles, &none,
+                                true)
+             : mixed_plan_device(plan);
+    if (rc) return rc;
+    const hbec::MRec* d_recs = own ? plan->d_rwrecs : plan->d_mrecs;
+    const hbec::MTile* d_tiles = own ? plan->d_rwtiles : plan->d_mtiles;
+    const uint64_t n_tiles = own ? plan->n_rwtiles : plan->n_mtiles;
+    int cus = 0;
+    rc = current_cus(&cus);
+    if (rc) return rc;
+    // The words first: which entries decode says which records the call needs
+    // and the largest count of rebuilt shards among them (gluewide.h gw_word: an
+    // entry whose missing data shards all lie beyond its length gathers).
+    std::vector<uint8_t> decodes(pats.size(), 0);
+    int rmax = 0;
+    for (uint64_t i = 0; i < plan->n_src; ++i) {
+        const ShardSet& o = pats[pattern_of[i]].out;
+        const uint64_t S = plan->src[i].shard_len, len = dst_lens[i];
+        if (S == 0 || len == 0 || hbec::gw_gathers(S, len, o.idx.data(), (int)o.idx.size())) continue;
+        decodes[pattern_of[i]] = 1;
+        rmax = std::max(rmax, (int)o.idx.size());
+    }
+    // The records of the masks some entry decodes with, one stride apart, then
+    // the gather record, which every other entry names (its position is past the
+    // sixteen bits of the word only when 65536 masks decode, and the gather tile
+    // reads no record: its survivors are 0..k-1 by definition).  Then one word per
+    // source entry and its destination; one launch per chunk of the list.
+    const uint32_t stride = hbec::gw_stride(k, rmax);
+    uint32_t n_rec = 0;
+    std::vector<uint32_t> stage;
+    for (size_t q = 0; q < pats.size(); ++q) {
+        if (!decodes[q]) continue;
+        const ShardSet& o = pats[q].out;
+        pats[q].rec = n_rec++;
+        stage.resize((size_t)n_rec * stride, 0u);
+        hbec::gw_pattern(stage.data() + (size_t)pats[q].rec * stride, k, o.surv.data(), o.idx.data(), (int)o.idx.size(),
+                         o.rows.data());
+    }
+    const uint32_t gather = n_rec++;
+    stage.resize((size_t)n_rec * stride, 0u);
+    hbec::gw_gather_pattern(stage.data() + (size_t)gather * stride, k);
+    const size_t rec_words = stage_patterns(
+        plan, pats, pattern_of, stage, [](PlanPattern&) {},
+        [&](uint64_t i, const PlanPattern& pp) {
+            return hbec::gw_word(plan->src[i].shard_len, dst_lens[i], pp.out.idx.data(), (int)pp.out.idx.size(), pp.rec,
+                                 gather);
+        });
+    const size_t dst_at = stage_glue_dsts(plan, dsts, dst_lens, stage);
+    return staged_launches(plan, stage, stream, [&](const uint32_t* d_pats) {
+        return walk_chunks(kGlueWide, n_tiles, "launch gf_glue_wide_plan", [&](uint64_t t0, uint32_t nt) {
+            return (hipError_t)hbec::launch_glue_wide_plan(k, rmax, stride, d_recs, d_tiles + t0, nt, d_pats + rec_words,
+                                                           d_pats + dst_at, d_pats, cus, stream, plan->shards);
+        });
+    });
+}
+
+int glue_plan_files_wide(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                         const uint64_t* content_lengths, uint64_t chunk_size, const uint8_t* patterns,
+                         uint32_t n_patterns, const uint32_t* pattern_of, void* const* object_dsts,
+                         hipStream_t stream) {
+    std::vector<void*> dsts;
+    std::vector<uint64_t> lens;
+    const int rc = glue_files_dsts(codec, plan, object_start, n_objects, content_lengths, chunk_size, object_dsts,
+                                   dsts, lens);
+    if (rc) return rc;
+    return glue_plan_wide(codec, plan, patterns, n_patterns, pattern_of, dsts.data(), lens.data(), stream);
+}
+
 // ---- the object bytes with the surplus shards checked (hbec_glue_plan_checked) ----
 
 // hbec_glue_plan_mixed that reads every present shard: a record per mask in use
@@ -2253,6 +2347,36 @@ int hbec_glue_plan_tile_bytes(void) { return hbec_mixed_plan_tile_bytes(); }
 
 int hbec_set_glue_plan_chunk_tiles(uint64_t tiles) {
     return set_chunk_tiles("hbec_set_glue_plan_chunk_tiles", kGlue, tiles);
+}
+
+int hbec_glue_plan_wide(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                        const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens, void* hip_stream) {
+    return hbec::guarded("hbec_glue_plan_wide", [&]() -> int {
+        return glue_plan_wide(codec, plan, patterns, n_patterns, pattern_of, dsts, dst_lens,
+                              static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_glue_plan_files_wide(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                              uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                              const uint8_t* patterns, uint32_t n_patterns, const uint32_t* pattern_of,
+                              void* const* object_dsts, void* hip_stream) {
+    return hbec::guarded("hbec_glue_plan_files_wide", [&]() -> int {
+        return glue_plan_files_wide(codec, plan, object_start, n_objects, content_lengths, chunk_size, patterns,
+                                    n_patterns, pattern_of, object_dsts, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_glue_wide_stats(uint64_t* kernel_launches) {
+    return hbec::guarded("hbec_glue_wide_stats", [&]() -> int {
+        if (!kernel_launches) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *kernel_launches = g_calls[kGlueWide].launches.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_set_glue_wide_chunk_tiles(uint32_t tiles) {
+    return set_chunk_tiles("hbec_set_glue_wide_chunk_tiles", kGlueWide, tiles);
 }
 
 int hbec_glue_plan_checked(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,

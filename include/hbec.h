@@ -795,6 +795,35 @@ int hbec_glue_plan_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
 int hbec_glue_plan_tile_bytes(void);
 /* test hook, as hbec_set_mixed_plan_chunk_tiles */
 int hbec_set_glue_plan_chunk_tiles(uint64_t tiles);
+/* hbec_glue_plan_mixed for wide stripes: ecGlue's loop (ecutils.go:134-186) for 1 <= k <= 32
+ * with 1 <= m <= 4 (16+4, 17+3, 20+4, 32+4), shards below 2^31 - 64 KiB, on every kind of
+ * plan, in one launch (per 2^31 - 1 tiles) whatever the entries, masks or lengths, where
+ * hbec_glue_plan_mixed above k = 12 queues a copy per present data shard and an apply per
+ * degraded entry.  Arguments, meaning and contract are hbec_glue_plan_mixed's word for word:
+ * entry i's data shards 0..k-1 back to back, their first dst_lens[i] bytes, at dsts[i] at any
+ * alignment; a present data shard is copied, a missing one is what ReconstructData computes
+ * from the entry's first k present shards; no shard byte is stored and no byte outside
+ * [dsts[i], dsts[i] + dst_lens[i]); dst_lens[i] = 0 skips the entry, dst_lens[i] <= k * S_i;
+ * no shard position at or past min(S_i, dst_lens[i]) is read.  An entry whose missing data
+ * shards all lie at or beyond dst_lens[i] decodes nothing and reads only the
+ * ceil(dst_lens[i] / S_i) data shards with a byte wanted.  Errors, all found before anything
+ * is queued and leaving the counter unmoved: hbec_glue_plan_mixed's of the patterns, then its
+ * own of the destinations, with their codes and messages; then HBEC_ERR_INVALID_ARG for any
+ * other (k, m) and for a plan that holds a longer shard: there is no per-entry route.  Calls
+ * on one plan from different streams take turns with the _mixed calls. */
+int hbec_glue_plan_wide(hbec_codec* codec, const hbec_plan* plan, const uint8_t* patterns, uint32_t n_patterns,
+                        const uint32_t* pattern_of, void* const* dsts, const uint64_t* dst_lens, void* hip_stream);
+/* hbec_glue_plan_files for wide stripes (ecutils.go:134-186): objects are cut into their
+ * entries' destinations exactly as hbec_glue_plan_files cuts them, with its errors, and then
+ * it is hbec_glue_plan_wide.  pattern_of stays per ENTRY. */
+int hbec_glue_plan_files_wide(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                              uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                              const uint8_t* patterns, uint32_t n_patterns, const uint32_t* pattern_of,
+                              void* const* object_dsts, void* hip_stream);
+/* launches since load of the wide glue kernel (ecutils.go:134-186); the call has no other route */
+int hbec_glue_wide_stats(uint64_t* kernel_launches);
+/* test hook for the wide glue (ecutils.go:134-186), as hbec_set_repair_wide_chunk_tiles (0 = default) */
+int hbec_set_glue_wide_chunk_tiles(uint32_t tiles);
 
 /* hbec_glue_plan_mixed with every PRESENT shard read once, the surplus ones checked and the
  * bytes they prove wrong corrected in what is written: read-repair on GET.  The reference's
