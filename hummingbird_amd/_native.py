@@ -219,6 +219,11 @@ _SIG = [
     ("hbec_split_plan_files_select", C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64),
                                                C.c_uint64, _P, _U8P, C.POINTER(C.c_uint32), C.c_uint32, _P]),
     ("hbec_split_select_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hbec_split_plan_wide", C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64), _P]),
+    ("hbec_split_plan_files_wide", C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64),
+                                             C.c_uint64, _P, _P]),
+    ("hbec_split_wide_stats", C.c_int, [C.POINTER(C.c_uint64)]),
+    ("hbec_set_split_wide_chunk_tiles", C.c_int, [C.c_uint32]),
     ("hbec_verify_host", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64, _U8P]),
     ("hbec_encode_host", C.c_int, [_P, C.POINTER(Stripe), C.c_uint64]),
     ("hbec_host_alloc", C.c_int, [C.c_size_t, C.POINTER(_P)]),

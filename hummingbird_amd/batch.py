@@ -899,6 +899,18 @@ class StripePlan:
         k+m shards are written whole; the source is read once.  lens[i] = 0
         skips the entry; otherwise ceil(lens[i] / k) must be the entry's shard
         length.  Queued on the stream."""
+        self._split_entries("hbec_split_plan", srcs, lens, stream)
+
+    def split_wide(self, srcs, lens, stream=None):
+        """split for wide stripes, 1 <= k <= 32 with 1 <= m <= 4 (16+4, 17+3,
+        20+4), in one launch on any kind of plan (hbec_split_plan_wide): the
+        same arguments and the same bytes written.  Above k = 12 split queues a
+        copy per data shard, a memset per padded one and an apply per entry.
+        Other shapes, m = 0 among them, and plans with a shard of 2^31 - 64 KiB
+        or more, raise: there is no per-entry route."""
+        self._split_entries("hbec_split_plan_wide", srcs, lens, stream)
+
+    def _split_entries(self, symbol, srcs, lens, stream):
         import numpy as np
 
         if len(srcs) != self._n or len(lens) != self._n:
@@ -906,17 +918,25 @@ class StripePlan:
         d = (C.c_void_p * max(1, self._n))(*[int(a) for a in srcs])
         ln = np.zeros(max(1, self._n), np.uint64)
         ln[:self._n] = [int(x) for x in lens]
-        check(N.lib().hbec_split_plan(self.enc.handle, self._h, d, ln.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      _stream_ptr(stream)))
+        check(getattr(N.lib(), symbol)(self.enc.handle, self._h, d, ln.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                       _stream_ptr(stream)))
 
     def split_files(self, srcs, stream=None):
         """split for a ``files=`` plan, object by object (hbec_split_plan_files):
         object g, its content length in bytes at the device address srcs[g],
         is written as its k+m shard files, which is ecSplit for the batch."""
+        self._split_objects("hbec_split_plan_files", "split_files", srcs, stream)
+
+    def split_files_wide(self, srcs, stream=None):
+        """split_files for wide stripes (hbec_split_plan_files_wide): the objects
+        are cut as split_files cuts them, and then it is split_wide."""
+        self._split_objects("hbec_split_plan_files_wide", "split_files_wide", srcs, stream)
+
+    def _split_objects(self, symbol, name, srcs, stream):
         import numpy as np
 
         if getattr(self, "_content_lengths", None) is None:
-            raise ValueError("split_files needs a plan built from files=")
+            raise ValueError(f"{name} needs a plan built from files=")
         n_obj = len(self._content_lengths)
         if len(srcs) != n_obj:
             raise ValueError("srcs needs one address per object")
@@ -924,7 +944,7 @@ class StripePlan:
         ln = np.zeros(max(1, n_obj), np.uint64)
         ln[:n_obj] = self._content_lengths
         starts = np.ascontiguousarray(self.object_start, dtype=np.uint32)
-        check(N.lib().hbec_split_plan_files(
+        check(getattr(N.lib(), symbol)(
             self.enc.handle, self._h, starts.ctypes.data_as(C.POINTER(C.c_uint32)), n_obj,
             ln.ctypes.data_as(C.POINTER(C.c_uint64)), int(self._chunk_size), d, _stream_ptr(stream)))
 
@@ -1210,6 +1230,19 @@ def glue_wide_stats():
 def set_glue_wide_chunk_tiles(tiles: int) -> None:
     """Test hook: wide glue kernel launches of at most `tiles` tiles (0 = default)."""
     check(N.lib().hbec_set_glue_wide_chunk_tiles(int(tiles)))
+
+
+def split_wide_stats():
+    """Since load, for StripePlan.split_wide / split_files_wide: launches of the
+    wide split kernel (`kernel_launches`); the call has no other route."""
+    a = C.c_uint64()
+    check(N.lib().hbec_split_wide_stats(C.byref(a)))
+    return {"kernel_launches": a.value}
+
+
+def set_split_wide_chunk_tiles(tiles: int) -> None:
+    """Test hook: wide split kernel launches of at most `tiles` tiles (0 = default)."""
+    check(N.lib().hbec_set_split_wide_chunk_tiles(int(tiles)))
 
 
 def heal_plan_stats():

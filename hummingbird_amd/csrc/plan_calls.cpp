@@ -24,7 +24,9 @@
 // gluewide.h, gluewide.hip) they walk the wide repair's list with its records.  The
 // inverse, every entry's shards from its object bytes (hbec_split_plan and
 // hbec_split_plan_files; splitplan.h, splitplan.hip), walks them too and stages
-// a source per entry; with a writers mask per entry (hbec_split_plan_select and
+// a source per entry; for stripes of up to 32 data shards (hbec_split_plan_wide,
+// hbec_split_plan_files_wide; splitwide.h, splitwide.hip) it walks the wide repair's
+// list with one record of its own; with a writers mask per entry (hbec_split_plan_select and
 // hbec_split_plan_files_select; splitselect.h, splitselect.hip) it writes the
 // chosen shards alone.  Any byte range of every entry (hbec_glue_plan_range and
 // hbec_glue_plan_files_range; gluerange.h, gluerange.hip) is the glue call with
@@ -72,6 +74,7 @@
 #include "shardplan.h"
 #include "splitplan.h"
 #include "splitselect.h"
+#include "splitwide.h"
 #include "vmixed.h"
 
 using hbec::current_cus;
@@ -84,7 +87,7 @@ namespace {
 
 // ---- counters and test hooks, a slot per call ----
 
-enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kGlueChecked, kGlueRangeChecked, kRepairWide, kGlueWide, kCalls };
+enum Call { kReconstruct = 0, kVerify, kRepair, kLocate, kHeal, kHash, kHashFiles, kGlue, kSplit, kGlueRange, kEtag, kCorrect, kSplitSelect, kGlueChecked, kGlueRangeChecked, kRepairWide, kGlueWide, kSplitWide, kCalls };
 struct CallSlot {
     std::atomic<uint64_t> launches{0};     // kernel launches
     std::atomic<uint64_t> second{0};       // per-stripe calls; skipped entries (locate, heal, correct); chains (hash calls)
@@ -1833,13 +1836,15 @@ int split_other_entry(const hbec_plan* plan, uint32_t i, const std::vector<uint8
     return hbec::apply_views(m, k, rows.data(), vin.data(), vout.data(), 1, S, stream);
 }
 
-int split_plan(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
-               hipStream_t stream) {
+// hbec_split_plan's argument checks, all before anything is queued; *any: some
+// entry was given bytes.  hbec_split_plan_wide makes the same.
+int check_split_srcs(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
+                     bool* any) {
     if (!codec || !plan || !srcs || !src_lens) return fail(HBEC_ERR_INVALID_ARG, "null argument");
     const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec), n = k + m;
     if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
     const uint64_t n_src = plan->n_src;
-    bool any = false;
+    *any = false;
     for (uint64_t i = 0; i < n_src; ++i) {  // zero-length entries too
         const uint64_t S = plan->src[i].shard_len, len = src_lens[i];
         const uint64_t src = reinterpret_cast<uintptr_t>(srcs[i]);
@@ -1852,14 +1857,24 @@ int split_plan(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs
             if (hbec::glue_overlaps(src, len, shard_addr(plan, (uint32_t)i, sh), S))
                 return fail(HBEC_ERR_INVALID_ARG, "source overlaps shard " + std::to_string(sh) +
                                                       " of its own entry (entry " + std::to_string(i) + ")");
-        any = true;
+        *any = true;
     }
+    return HBEC_OK;
+}
+
+int split_plan(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
+               hipStream_t stream) {
+    bool any = false;
+    int rc = check_split_srcs(codec, plan, srcs, src_lens, &any);
+    if (rc) return rc;
+    const int k = plan->k, m = plan->m, n = k + m;
+    const uint64_t n_src = plan->n_src;
     if (!any) return HBEC_OK;  // nothing given
     // a plan of m = 0 has a list of the call's own (plan_internal.h)
     const bool own = m == 0;
-    int rc = own ? walk_list_device(plan, 1, &plan->sp_built, &plan->d_sprecs, &plan->d_sptiles, &plan->n_sptiles,
-                                    &plan->sp_other)
-                 : mixed_plan_device(plan);
+    rc = own ? walk_list_device(plan, 1, &plan->sp_built, &plan->d_sprecs, &plan->d_sptiles, &plan->n_sptiles,
+                                &plan->sp_other)
+             : mixed_plan_device(plan);
     if (rc) return rc;
     const hbec::MRec* d_recs = own ? plan->d_sprecs : plan->d_mrecs;
     const hbec::MTile* d_tiles = own ? plan->d_sptiles : plan->d_mtiles;
@@ -1916,15 +1931,17 @@ int split_plan(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs
 
 // ---- whole objects of a files plan into their shard files (hbec_split_plan_files) ----
 
-int split_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+// hbec_split_plan_files' checks of its own and the cut of every object into its
+// entries' pieces; hbec_split_plan_files_wide makes the same.
+int split_files_srcs(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
                      const uint64_t* content_lengths, uint64_t chunk_size, const void* const* object_srcs,
-                     hipStream_t stream) {
+                     std::vector<const void*>& srcs, std::vector<uint64_t>& lens) {
     if (!codec || !plan || !content_lengths || !object_srcs) return fail(HBEC_ERR_INVALID_ARG, "null argument");
     const int k = hbec_data_shards(codec), m = hbec_parity_shards(codec);
     if (k != plan->k || m != plan->m) return fail(HBEC_ERR_INVALID_ARG, "plan built for another (k, m)");
     const uint64_t n_src = plan->n_src;
-    std::vector<const void*> srcs((size_t)std::max<uint64_t>(1, n_src), nullptr);
-    std::vector<uint64_t> lens((size_t)std::max<uint64_t>(1, n_src), 0u);
+    srcs.assign((size_t)std::max<uint64_t>(1, n_src), nullptr);
+    lens.assign((size_t)std::max<uint64_t>(1, n_src), 0u);
     if (n_src) {
         if (const char* why = hbec::files_check_objects(object_start, n_objects, n_src))
             return fail(HBEC_ERR_INVALID_ARG, why);
@@ -1945,7 +1962,79 @@ int split_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* o
             }
         }
     }
+    return HBEC_OK;
+}
+
+int split_plan_files(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                     const uint64_t* content_lengths, uint64_t chunk_size, const void* const* object_srcs,
+                     hipStream_t stream) {
+    std::vector<const void*> srcs;
+    std::vector<uint64_t> lens;
+    const int rc = split_files_srcs(codec, plan, object_start, n_objects, content_lengths, chunk_size, object_srcs,
+                                    srcs, lens);
+    if (rc) return rc;
     return split_plan(codec, plan, srcs.data(), lens.data(), stream);
+}
+
+// ---- hbec_split_plan's contract for 1 <= k <= 32 in one launch (hbec_split_plan_wide) ----
+
+int split_plan_wide(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
+                    hipStream_t stream) {
+    bool any = false;
+    int rc = check_split_srcs(codec, plan, srcs, src_lens, &any);
+    if (rc) return rc;
+    const int k = plan->k, m = plan->m, n = k + m;
+    const uint64_t n_src = plan->n_src;
+    // no per-entry route: what the kernel does not take is refused
+    if (!hbec::rw_shape(k, m)) return fail(HBEC_ERR_INVALID_ARG, "hbec_split_plan_wide takes 1 <= k <= 32 with 1 <= m <= 4");
+    for (uint64_t i = 0; i < n_src; ++i)
+        if (!hbec::pos32_shard(plan->src[i].shard_len))
+            return fail(HBEC_ERR_INVALID_ARG, "shard of 2^31 - 64 KiB bytes or more (entry " + std::to_string(i) + ")");
+    if (!any) return HBEC_OK;  // nothing given
+    // k <= 12: the mixed family's records and list; wider: the wide repair's
+    const bool own = !hbec::mp_fast_shape(k, m);
+    std::vector<uint32_t> none;
+    rc = own ? walk_list_device(plan, m, &plan->rw_built, &plan->d_rwrecs, &plan->d_rwtiles, &plan->n_rwtiles, &none,
+                                true)
+             : mixed_plan_device(plan);
+    if (rc) return rc;
+    const hbec::MRec* d_recs = own ? plan->d_rwrecs : plan->d_mrecs;
+    const hbec::MTile* d_tiles = own ? plan->d_rwtiles : plan->d_mtiles;
+    const uint64_t n_tiles = own ? plan->n_rwtiles : plan->n_mtiles;
+    int cus = 0;
+    rc = current_cus(&cus);
+    if (rc) return rc;
+    // The call's one record (the encode rows: rows k..k+m-1 of the coding matrix),
+    // one word per source entry, then its piece; one launch per chunk of the list.
+    std::vector<uint8_t> mat((size_t)n * k);
+    hbec_matrix(codec, mat.data());
+    const size_t rec_words = hbec::rw_record_words(k, m);
+    std::vector<uint32_t> stage(rec_words + 5 * (size_t)n_src, 0u);
+    hbec::sw_pattern(stage.data(), k, m, mat.data() + (size_t)k * k);
+    const size_t src_at = rec_words + (size_t)n_src;
+    for (uint64_t i = 0; i < n_src; ++i) {
+        const uint64_t src = reinterpret_cast<uintptr_t>(srcs[i]), len = src_lens[i];
+        stage[rec_words + i] = hbec::sw_word(m, plan->src[i].shard_len, len);
+        uint32_t* d = stage.data() + src_at + 4 * i;
+        d[0] = (uint32_t)src, d[1] = (uint32_t)(src >> 32), d[2] = (uint32_t)len, d[3] = (uint32_t)(len >> 32);
+    }
+    return staged_launches(plan, stage, stream, [&](const uint32_t* d_pats) {
+        return walk_chunks(kSplitWide, n_tiles, "launch gf_split_wide_plan", [&](uint64_t t0, uint32_t nt) {
+            return (hipError_t)hbec::launch_split_wide_plan(k, m, d_recs, d_tiles + t0, nt, d_pats + rec_words,
+                                                            d_pats + src_at, d_pats, cus, stream, plan->shards);
+        });
+    });
+}
+
+int split_plan_files_wide(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start, uint32_t n_objects,
+                          const uint64_t* content_lengths, uint64_t chunk_size, const void* const* object_srcs,
+                          hipStream_t stream) {
+    std::vector<const void*> srcs;
+    std::vector<uint64_t> lens;
+    const int rc = split_files_srcs(codec, plan, object_start, n_objects, content_lengths, chunk_size, object_srcs,
+                                    srcs, lens);
+    if (rc) return rc;
+    return split_plan_wide(codec, plan, srcs.data(), lens.data(), stream);
 }
 
 // ---- chosen shards of every entry from its object bytes (hbec_split_plan_select) ----
@@ -2551,6 +2640,34 @@ int hbec_split_plan_files_select(hbec_codec* codec, const hbec_plan* plan, const
 
 int hbec_split_select_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls) {
     return call_stats("hbec_split_select_stats", kSplitSelect, kernel_launches, per_stripe_calls);
+}
+
+int hbec_split_plan_wide(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
+                         void* hip_stream) {
+    return hbec::guarded("hbec_split_plan_wide", [&]() -> int {
+        return split_plan_wide(codec, plan, srcs, src_lens, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_split_plan_files_wide(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                               uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                               const void* const* object_srcs, void* hip_stream) {
+    return hbec::guarded("hbec_split_plan_files_wide", [&]() -> int {
+        return split_plan_files_wide(codec, plan, object_start, n_objects, content_lengths, chunk_size, object_srcs,
+                                     static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int hbec_split_wide_stats(uint64_t* kernel_launches) {
+    return hbec::guarded("hbec_split_wide_stats", [&]() -> int {
+        if (!kernel_launches) return fail(HBEC_ERR_INVALID_ARG, "null argument");
+        *kernel_launches = g_calls[kSplitWide].launches.load(std::memory_order_relaxed);
+        return HBEC_OK;
+    });
+}
+
+int hbec_set_split_wide_chunk_tiles(uint32_t tiles) {
+    return set_chunk_tiles("hbec_set_split_wide_chunk_tiles", kSplitWide, tiles);
 }
 
 }  // extern "C"

@@ -1169,6 +1169,32 @@ int hbec_split_plan_files_select(hbec_codec* codec, const hbec_plan* plan, const
 /* ecSplit with its writers (ecutils.go:26-72, line 63) batch call: launches since load of
  * the select kernel, and copies, memsets and applies of the per-entry route */
 int hbec_split_select_stats(uint64_t* kernel_launches, uint64_t* per_stripe_calls);
+/* hbec_split_plan for wide stripes: ecSplit's loop (ecutils.go:26-72) for 1 <= k <= 32 with
+ * 1 <= m <= 4 (16+4, 17+3, 20+4, 32+4), shards below 2^31 - 64 KiB, on every kind of plan, in
+ * one launch (per 2^31 - 1 tiles) whatever the entries or lengths, where hbec_split_plan above
+ * k = 12 queues a copy per data shard, a memset per padded one and an apply per entry.
+ * Arguments, meaning and contract are hbec_split_plan's word for word: entry i's piece
+ * [srcs[i], srcs[i] + src_lens[i]) at any alignment; data shard j its bytes [j S_i, (j+1) S_i)
+ * with zeros from position src_lens[i] - j S_i on (whole trailing shards where S_i < k); parity
+ * shard r row k + r of the coding matrix over them; all k+m shards written whole and nothing
+ * else; the source read once and not modified, no 16-byte block without a byte of the piece
+ * read; src_lens[i] = 0 skips the entry.  Errors, all found before anything is queued and
+ * leaving the counter unmoved: hbec_split_plan's, in its order and with its messages; then
+ * HBEC_ERR_INVALID_ARG for any other (k, m), m = 0 among them, and for a plan that holds a
+ * longer shard: there is no per-entry route.  A call in which no entry has bytes launches
+ * nothing.  Calls on one plan from different streams take turns with the _mixed calls. */
+int hbec_split_plan_wide(hbec_codec* codec, const hbec_plan* plan, const void* const* srcs, const uint64_t* src_lens,
+                         void* hip_stream);
+/* hbec_split_plan_files for wide stripes (ecutils.go:26-72): objects are cut into their
+ * entries' pieces exactly as hbec_split_plan_files cuts them, with its errors, and then it is
+ * hbec_split_plan_wide. */
+int hbec_split_plan_files_wide(hbec_codec* codec, const hbec_plan* plan, const uint32_t* object_start,
+                               uint32_t n_objects, const uint64_t* content_lengths, uint64_t chunk_size,
+                               const void* const* object_srcs, void* hip_stream);
+/* launches since load of the wide split kernel (ecutils.go:26-72); the call has no other route */
+int hbec_split_wide_stats(uint64_t* kernel_launches);
+/* test hook for the wide split (ecutils.go:26-72), as hbec_set_glue_wide_chunk_tiles (0 = default) */
+int hbec_set_split_wide_chunk_tiles(uint32_t tiles);
 
 /* Host-memory batches (streaming host path): stripes in HOST memory (same
  * ecSplit layout), coded through a pinned staging ring — CPU gather, H2D,
